@@ -13,8 +13,10 @@ device merge; ``--search plane`` keeps the point-to-point plane) -> fused cosine
 threshold + top-k on each shard (vecsearch.hip) -> build the Answer prompt from the top-k chunks
 (pre-tokenized at ingest) -> Phi-3-mini prefill (~2.9k tokens/query) + decode MAX_NEW tokens at
 T=0.2 (HIP kernels, HIP graphs) -> confidence = avg similarity x mean token probability ->
-detokenize. After the timed steps at N > 1, the multi-GPU blocks (parallel/collective_bench.py)
-time the fabric mechanisms into the same JSON line.
+detokenize. A plain run ends there: setup, warmup, the timed steps, the JSON line (``--dump-outputs
+DIR`` also writes what the last timed step returned as .npy files). With ``--full`` the run goes on
+to the per-phase breakdowns, the batch-1 cache-miss latency, ingest and, at N > 1, the multi-GPU
+blocks (parallel/collective_bench.py), which time the fabric mechanisms into the same JSON line.
 
 Synthetic data (no network): random-init weights of the named architectures, random unit vectors
 for the 100k background chunks per GPU (their token ids drawn from the locally trained BPE vocab),
@@ -22,7 +24,7 @@ synthetic questions; each query filters on `--docs-per-query` random documents s
 shards. MIN_SIMILARITY is set to -1 so every query retrieves exactly top_k chunks (random weights
 make the reference's 0.7 floor meaningless; -1 is the MOST work per query, never less).
 
-Launch: python bench.py [--gpus N --steps K --warmup W]. With N > 1 and no WORLD_SIZE in the
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. With N > 1 and no WORLD_SIZE in the
 environment, this process launches N ranks itself (python -m torch.distributed.run, one rank per GPU)
 before anything touches the GPU, relays their output and exits with their status; under an external
 torchrun (WORLD_SIZE set) it is one rank, and WORLD_SIZE != --gpus is an error. Every rank is an
@@ -133,6 +135,30 @@ def doc_names(world: int, ndocs: int) -> list[list[str]]:
     return names
 
 
+def dump_outputs(path: str, last: dict, res, max_new: int) -> None:
+    """What the last timed QA step returned, as <path>/<name>.npy: the question embeddings [B, d] and
+    the search's scores / chunk ids [B, top_k] (-1: no hit), then per query the answer's text as
+    Unicode code points [B, 32 * max_new] (-1 padded; longer texts cut) with its true length [B], and
+    the confidence [B]. ids, lengths and confidences are float64 (chunk ids pass 2^24), the rest
+    float32; a few MB at the default sizes."""
+    os.makedirs(path, exist_ok=True)
+    width = 32 * max_new
+    cp = np.full((len(res), width), -1.0, dtype=np.float32)
+    for b, (txt, _) in enumerate(res):
+        o = [ord(c) for c in txt[:width]]
+        cp[b, :len(o)] = o
+    arrays = {
+        "query_embeddings": last["qv"].float().cpu().numpy().astype(np.float32),
+        "search_scores": np.asarray(last["scores"], dtype=np.float32),
+        "search_ids": np.asarray(last["ids"], dtype=np.float64),
+        "answer_codepoints": cp,
+        "answer_chars": np.array([len(txt) for txt, _ in res], dtype=np.float64),
+        "confidence": np.array([c for _, c in res], dtype=np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -200,10 +226,24 @@ def main():
     ap.add_argument("--block-budget-s", type=float, default=360.0,
                     help="N > 1: wall budget of each multi-GPU block; past it every rank ends the run and rank 0 "
                          "prints the JSON line with the blocks done so far (a hung collective cannot eat the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed QA steps also measure everything else: the per-phase breakdowns, the "
+                         "batch-1 cache-miss latency, ingest (docs/min, single-document latency) and, at N > 1, the "
+                         "multi-GPU blocks. Without it the run sets up, warms up, times --steps QA steps and prints "
+                         "the JSON line (those keys null); --latency-reps, --ingest-*, --breakdown, --multi-iters, "
+                         "--serving-requests and --tp70b* act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed QA step returned as DIR/<name>.npy (float32 / float64): the "
+                         "question embeddings, the search scores and chunk ids, each answer's text as code points "
+                         "(fixed width, -1 padded) and its confidence. At N > 1 every rank writes DIR/rank<r>/")
     a = ap.parse_args()
 
     if a.ingest_docs is None:
         a.ingest_docs = a.batch
+    if not a.full:  # a plain run: the headline's timed steps only
+        a.latency_reps = a.ingest_docs = a.breakdown = 0
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     info = init_from_env()
     W, R = info.world, info.rank
     if any(k.startswith("DA_") for k in os.environ):  # A/B arms (bench/ab_arms.py): only when asked
@@ -278,12 +318,15 @@ def main():
             return sc.float().cpu().numpy(), gid.cpu().numpy()
         return plane.submit(qv.float().cpu().numpy(), a.top_k, a.min_sim, filters).result()
 
+    last_step: dict = {}
+
     def qa_items(step: int, B: int):
         """A QA step up to the answers: embed the questions, sharded search, context chunks."""
         qs = [tg.question() for _ in range(B)]
         filters = make_filters(step)
         qv = eng.embed(qs)
         s_h, id_h = search(qv, filters)
+        last_step.update(qv=qv, scores=s_h, ids=id_h)  # references only: --dump-outputs reads them after the timing
         items = []
         for b in range(B):
             valid = id_h[b] >= 0
@@ -324,7 +367,8 @@ def main():
     plen = []
     if overlap:
         eng.gen.stats.pop("overlap_moves", None); eng.gen.stats.pop("overlap_decode_join_s", None)
-        _, waves = qa_steps_overlapped(100, a.steps, a.batch)
+        res_waves, waves = qa_steps_overlapped(100, a.steps, a.batch)
+        res = res_waves[-1]
         log(info, f"overlap: prefill moved to the full chip at (layer, s) {eng.gen.stats.get('overlap_moves')}, "
                   f"decode joined after {eng.gen.stats.get('overlap_decode_join_s')} s")
         for items in waves:
@@ -337,6 +381,8 @@ def main():
     dt = time.perf_counter() - t0
     dt_max = all_reduce_max(dt, dev)
     qps = DP * a.batch * a.steps / dt_max
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs if W == 1 else os.path.join(a.dump_outputs, f"rank{R}"), last_step, res, a.max_new)
 
     # ---- phase breakdown of one extra (untimed) QA step, device-synchronized at phase boundaries ----
     def breakdown(B: int, seed: int) -> dict:
@@ -531,7 +577,7 @@ def main():
     # block overruns --block-budget-s (a hung collective). The graph-captured RCCL arms (the served
     # TP fallback) run last, in blocks of their own: the one form that has never run on a node.
     multi: dict = {}
-    if W > 1:
+    if W > 1 and a.full:
         from docagents_amd.parallel import collective_bench as CB
         B_cur = a.batch
 

@@ -1,7 +1,8 @@
 """Tokenizers built locally (there is no network to fetch pretrained vocabularies).
 
-* Encoder: BERT-style WordPiece (lowercase, [CLS]/[SEP]/[PAD]/[UNK]/[MASK]) trained with HF
-  ``tokenizers`` on the deterministic synthetic corpus, vocab capped at the encoder's vocab size.
+* Encoder: BERT-style WordPiece (lowercase, [CLS]/[SEP]/[PAD]/[UNK]/[MASK]) whose pieces are BPE
+  merges trained with HF ``tokenizers`` on the deterministic synthetic corpus, each kept as a word
+  start and as a ``##`` continuation, vocab capped at the encoder's vocab size.
 * Decoder: byte-level BPE with the Phi-3 chat special tokens (``<|system|>``, ``<|user|>``,
   ``<|assistant|>``, ``<|end|>``, ``<|endoftext|>``), vocab capped at the decoder's vocab size.
 
@@ -43,11 +44,22 @@ def _locked_build(path: Path, builder):
 
 
 def _train_encoder(vocab_size: int) -> Tokenizer:
-    tok = Tokenizer(models.WordPiece(unk_token="[UNK]", max_input_chars_per_word=100))
+    # The pieces are learned as plain BPE merges over the BERT-pre-tokenized words and enter the
+    # WordPiece vocabulary twice, as word starts and as "##" continuations. WordPieceTrainer itself
+    # numbers the "##" characters in the iteration order of a randomly seeded hash map and breaks
+    # merge ties by those ids: two processes trained different vocabularies from the same corpus.
+    # Without a continuation prefix the trainer's alphabet is sorted and the merges are repeatable.
+    bpe = Tokenizer(models.BPE())
+    bpe.normalizer = normalizers.BertNormalizer(lowercase=True)
+    bpe.pre_tokenizer = pre_tokenizers.BertPreTokenizer()
+    tr = trainers.BpeTrainer(vocab_size=(vocab_size - len(ENC_SPECIAL)) // 2, special_tokens=[], min_frequency=2)
+    bpe.train_from_iterator(corpus(1_500_000, seed=11), trainer=tr)
+    pieces = [t for t, _ in sorted(bpe.get_vocab().items(), key=lambda kv: kv[1])]
+    vocab = {t: i for i, t in enumerate(ENC_SPECIAL + pieces + ["##" + t for t in pieces])}
+    tok = Tokenizer(models.WordPiece(vocab=vocab, unk_token="[UNK]", max_input_chars_per_word=100))
     tok.normalizer = normalizers.BertNormalizer(lowercase=True)
     tok.pre_tokenizer = pre_tokenizers.BertPreTokenizer()
-    tr = trainers.WordPieceTrainer(vocab_size=vocab_size, special_tokens=ENC_SPECIAL, min_frequency=2)
-    tok.train_from_iterator(corpus(1_500_000, seed=11), trainer=tr)
+    tok.add_special_tokens(ENC_SPECIAL)
     cls, sep = tok.token_to_id("[CLS]"), tok.token_to_id("[SEP]")
     tok.post_processor = processors.TemplateProcessing(single="[CLS] $A [SEP]", pair="[CLS] $A [SEP] $B [SEP]",
                                                        special_tokens=[("[CLS]", cls), ("[SEP]", sep)])
@@ -67,7 +79,7 @@ def _train_decoder(vocab_size: int) -> Tokenizer:
 
 @lru_cache(maxsize=8)
 def encoder_tokenizer(vocab_size: int = 30522) -> Tokenizer:
-    p = _cache_dir() / f"enc_wordpiece_{vocab_size}_{_VERSION}.json"
+    p = _cache_dir() / f"enc_wordpiece_{vocab_size}_v2.json"  # v1: WordPieceTrainer, not repeatable
     if p.exists():
         return Tokenizer.from_file(str(p))
     return _locked_build(p, lambda: _train_encoder(vocab_size))

@@ -9,7 +9,7 @@ mkdir -p $OUT
 for i in $(seq 1 $N); do
   for arm in A B; do
     if [ $arm = A ]; then E=$A; else E=$B; fi
-    env $E timeout -k 10 400 python bench.py --steps 4 --warmup 1 --latency-reps 3 --ingest-docs 0 $ARGS > $OUT/${arm}_$i.json 2> $OUT/${arm}_$i.err || { tail -5 $OUT/${arm}_$i.err; exit 1; }
+    env $E timeout -k 10 400 python bench.py --full --steps 4 --warmup 1 --latency-reps 3 --ingest-docs 0 $ARGS > $OUT/${arm}_$i.json 2> $OUT/${arm}_$i.err || { tail -5 $OUT/${arm}_$i.err; exit 1; }
     echo "$arm[$E] $(python -c "import json,sys; d=json.load(open('$OUT/${arm}_$i.json')); print(d['value'], d['ms_per_step'], d.get('p50_cache_miss_ms'))")"
   done
 done

@@ -13,10 +13,10 @@ rc=$?; echo "pytest rc=$rc"; tail -4 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -1 $OUT/smoke.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json
 [ $rc -ne 0 ] && { tail -5 $OUT/bench.err; exit $rc; }
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o bench -- python3 $R/bench.py --steps 1 --warmup 1 --latency-reps 1 --ingest-docs 16 --breakdown 0 > $R/$OUT/prof_bench.json 2> $R/$OUT/prof_bench.err)
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o bench -- python3 $R/bench.py --full --steps 1 --warmup 1 --latency-reps 1 --ingest-docs 16 --breakdown 0 > $R/$OUT/prof_bench.json 2> $R/$OUT/prof_bench.err)
 rc=$?; echo "prof rc=$rc"
 [ $rc -ne 0 ] && exit $rc
 python - <<PY

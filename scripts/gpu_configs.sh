@@ -24,34 +24,34 @@ run() {  # name timeout cmd...
   return $rc
 }
 case ${1:-c4} in
-  c3) run c3 900 python bench.py --llm llama3-8b --pdf-ingest ;;
-  c4) run c4 600 python bench.py --enc bge-large --index-rows 1250000 --latency-reps 3 --ingest-docs 32 ;;
-  c4f16) run c4f16 600 python bench.py --enc bge-large --enc-dtype fp16 --index-rows 1250000 --latency-reps 3 \
+  c3) run c3 900 python bench.py --full --llm llama3-8b --pdf-ingest ;;
+  c4) run c4 600 python bench.py --full --enc bge-large --index-rows 1250000 --latency-reps 3 --ingest-docs 32 ;;
+  c4f16) run c4f16 600 python bench.py --full --enc bge-large --enc-dtype fp16 --index-rows 1250000 --latency-reps 3 \
            --ingest-docs 32 ;;
-  llama70b) run llama70b 1200 python bench.py --llm llama3-70b --enc bge-large --batch 16 --steps 2 --warmup 1 \
+  llama70b) run llama70b 1200 python bench.py --full --llm llama3-70b --enc bge-large --batch 16 --steps 2 --warmup 1 \
               --latency-reps 2 --ingest-docs 4 --ingest-batches 1 ;;
   rank2) DA_DIST_BACKEND=gloo run rank2 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-           --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --batch 16 \
+           --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 2 --warmup 1 --batch 16 \
            --latency-reps 2 --ingest-docs 4 --ingest-batches 1 ;;
   tp2) DA_DIST_BACKEND=gloo run tp2 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-         --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --tp 2 --index-kind ivfflat --steps 1 \
+         --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 2 --tp 2 --index-kind ivfflat --steps 1 \
          --warmup 1 --batch 8 --latency-reps 1 --ingest-docs 0 ;;
   c5) DA_DIST_BACKEND=gloo run c5 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-        --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 8 --llm llama3-70b --tp 8 --enc bge-large \
+        --master-addr 127.0.0.1 --master-port 29535 bench.py --full --gpus 8 --llm llama3-70b --tp 8 --enc bge-large \
         --enc-dtype fp8 --index-kind ivfflat --batch 2 --steps 1 --warmup 1 --latency-reps 1 --ingest-docs 0 \
         --max-new 8 --breakdown 0 ;;  # gloo TP all-reduces through the host: a path check, not a perf number
   r2) DA_DIST_BACKEND=gloo run r2 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29536 bench.py --gpus 2 --steps 2 --warmup 1 --batch 4 \
+        --master-addr 127.0.0.1 --master-port 29536 bench.py --full --gpus 2 --steps 2 --warmup 1 --batch 4 \
         --latency-reps 2 --ingest-docs 4 --ingest-batches 1 --ingest-latency-reps 2 ;;
   r4) DA_DIST_BACKEND=gloo run r4 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-        --master-addr 127.0.0.1 --master-port 29540 bench.py --gpus 4 --steps 1 --warmup 1 --batch 4 \
+        --master-addr 127.0.0.1 --master-port 29540 bench.py --full --gpus 4 --steps 1 --warmup 1 --batch 4 \
         --latency-reps 1 --ingest-docs 2 --ingest-batches 1 --ingest-latency-reps 1 --max-new 8 --breakdown 0 ;;
   r8) DA_DIST_BACKEND=gloo run r8 1100 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-        --master-addr 127.0.0.1 --master-port 29537 bench.py --gpus 8 --steps 1 --warmup 1 --batch 4 \
+        --master-addr 127.0.0.1 --master-port 29537 bench.py --full --gpus 8 --steps 1 --warmup 1 --batch 4 \
         --latency-reps 1 --ingest-docs 2 --ingest-batches 1 --ingest-latency-reps 1 --max-new 8 \
         --tp70b-batches 1,2 --breakdown 0 ;;
   c4full) DA_DIST_BACKEND=gloo run c4full 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-            --master-addr 127.0.0.1 --master-port 29538 bench.py --gpus 8 --enc bge-large --enc-dtype fp16 \
+            --master-addr 127.0.0.1 --master-port 29538 bench.py --full --gpus 8 --enc bge-large --enc-dtype fp16 \
             --index-rows 1250000 --batch 4 --steps 2 --warmup 1 --latency-reps 2 --ingest-docs 0 --max-new 8 \
             --breakdown 0 --tp70b off --search rccl \
           && DA_DIST_BACKEND=gloo run c4recall 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_rank_json_schema():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "2"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-rehearsal",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-rehearsal", "--full",
            "--enc", "tiny-enc", "--llm", "tiny-dec", "--batch", "2", "--steps", "1", "--warmup", "0",
            "--latency-reps", "2", "--ingest-docs", "2", "--ingest-batches", "1", "--ingest-latency-reps", "2",
            "--index-rows", "2000", "--multi-iters", "3", "--breakdown", "0", "--max-new", "4",
@@ -88,7 +88,7 @@ def test_bench_watchdog_ends_a_hung_block_with_the_json_line():
     done so far and the block that hung; the launcher's status stays 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(OMP_NUM_THREADS="2", DA_BENCH_HANG_BLOCK="tp_decode")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-rehearsal",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-rehearsal", "--full",
            "--enc", "tiny-enc", "--llm", "tiny-dec", "--batch", "2", "--steps", "1", "--warmup", "0",
            "--latency-reps", "1", "--ingest-docs", "0", "--index-rows", "2000", "--multi-iters", "2",
            "--breakdown", "0", "--max-new", "4", "--serving-requests", "4", "--block-budget-s", "3"]
