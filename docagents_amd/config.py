@@ -51,6 +51,9 @@ class Config:
     llm_arch: str = field(default="phi3-mini", metadata={"env": "LLM_ARCH"})
     embed_dim: int = field(default=0, metadata={"env": "EMBED_DIM"})  # 0 -> encoder hidden size
     dtype: str = field(default="bf16", metadata={"env": "DTYPE"})
+    # decoder weight storage: bf16, or fp8 = the decoder quantised per output row to OCP e4m3 with an
+    # e4m3 copy of every matmul weight that the batch-1 decode GEMVs stream (TP_SIZE=1 only)
+    llm_weight_dtype: str = field(default="bf16", metadata={"env": "LLM_WEIGHT_DTYPE"})
     tp_size: int = field(default=1, metadata={"env": "TP_SIZE"})
     index_shards: int = field(default=1, metadata={"env": "INDEX_SHARDS"})
     index_kind: str = field(default="flat", metadata={"env": "INDEX_KIND"})
@@ -133,10 +136,11 @@ class Config:
     def replace(self, **kw) -> "Config":
         return dataclasses.replace(self, **kw)
 
-    # engine compute dtypes (the encoder's; the decoder is bf16): bf16 everywhere; fp16 encoder
+    # engine compute dtypes (the encoder's; the decoder's weights: LLM_WEIGHT_DTYPE): bf16 everywhere; fp16 encoder
     # (f16 MFMA GEMMs + flash, fp16 LayerNorm: BASELINE config 4); fp8 (OCP e4m3) encoder GEMMs.
     # Anything else is refused at startup, never run as something else.
     ENGINE_DTYPES = ("bf16", "fp16", "fp8")
+    LLM_WEIGHT_DTYPES = ("bf16", "fp8")
 
     def validate_engine(self) -> "Config":
         """Startup check of the engine keys whose wrong value would otherwise silently run a
@@ -147,6 +151,12 @@ class Config:
             raise ValueError(f"INDEX_KIND={self.index_kind!r} is not supported (flat | ivfflat)")
         if self.tp_size < 1:
             raise ValueError(f"TP_SIZE={self.tp_size} must be >= 1")
+        if self.llm_weight_dtype not in self.LLM_WEIGHT_DTYPES:
+            raise ValueError(f"LLM_WEIGHT_DTYPE={self.llm_weight_dtype!r} is not supported "
+                             f"(choose one of {', '.join(self.LLM_WEIGHT_DTYPES)})")
+        if self.llm_weight_dtype == "fp8" and self.tp_size > 1:
+            # quantising per TP shard is a different model from quantising the whole
+            raise ValueError("LLM_WEIGHT_DTYPE=fp8 needs TP_SIZE=1")
         if self.search_transport not in ("plane", "rccl"):
             raise ValueError(f"SEARCH_TRANSPORT={self.search_transport!r} is not supported (plane | rccl)")
         if self.search_transport == "rccl" and self.tp_size > 1:

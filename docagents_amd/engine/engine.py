@@ -42,7 +42,8 @@ class Engine:
                  max_new_tokens: int = 64, summary_max_new: int = 128, index_kind: str = "flat",
                  ivf_lists: int = 100, ivf_probes: int = 1, load_llm: bool = True, load_encoder: bool = True,
                  use_graphs: bool = True, embed_max_tokens: int = 65536, enc_dtype: str = "bf16",
-                 share_prefix: bool = True, overlap_waves: bool = False, kv_cache_gb: float = 0.0):
+                 share_prefix: bool = True, overlap_waves: bool = False, kv_cache_gb: float = 0.0,
+                 llm_weight_dtype: str = "bf16"):
         self.device = torch.device(device)
         self.lock = threading.RLock()      # the decoder / generator (one GPU thread drives it)
         self.enc_lock = threading.RLock()  # the encoder: the fast embed lane and the batcher share it
@@ -64,7 +65,9 @@ class Engine:
         self.decoder = None
         self.gen = None
         if load_llm:
-            self.decoder = LlamaDecoder(self.dec_cfg, self.device, seed=seed, tp=tp)
+            # "fp8": an e4m3 copy of the matmul weights (+ 1 byte per weight of HBM) that the batch-1
+            # decode GEMVs stream; auto_batch below sizes the KV cache from what is free after it
+            self.decoder = LlamaDecoder(self.dec_cfg, self.device, seed=seed, tp=tp, weight_dtype=llm_weight_dtype)
             if max_batch <= 0:
                 max_batch = self.auto_batch(max_seq, overlap_waves, kv_gb=kv_cache_gb)
             # + 1 dummy slot (padded graph rows) + 2 prompt-head slots (ContinuousScheduler heads)

@@ -217,12 +217,21 @@ class KVCache:
         return cfg.layers * 2 * slots * (cfg.kv_heads // tp_size) * max_seq * cfg.head_dim * 2
 
 
+WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMV chain
+
+
 class LlamaDecoder:
     unit_gains = False  # set by _fold_norm_gains
     layer_hook = None   # prefill: called with the layer index before each layer (stream steering)
 
     def __init__(self, cfg: DecoderConfig, device="cuda", seed: int = 0, tp: TPContext | None = None,
-                 weights: dict | None = None):
+                 weights: dict | None = None, weight_dtype: str = "bf16"):
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype={weight_dtype!r} is not supported ({' | '.join(WEIGHT_DTYPES)})")
+        if weight_dtype == "fp8" and tp is not None and tp.size > 1:
+            # quantising per shard is a different model from quantising the whole
+            raise ValueError("weight_dtype='fp8' needs TP size 1")
+        self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.device = torch.device(device)
         self.ops = get_ops(self.device)
@@ -234,6 +243,8 @@ class LlamaDecoder:
         self.hl, self.kl = cfg.heads // t, cfg.kv_heads // t
         self.w = weights if weights is not None else random_weights(cfg, self.device, seed, self.tp.rank, t)
         self._fold_norm_gains()
+        if weight_dtype == "fp8":
+            self._quantise_weights_fp8()
         self.cos_sin = rope_table(cfg.max_pos, cfg.head_dim, cfg.rope_theta, self.device)
         self.cache: KVCache | None = None
 
@@ -251,6 +262,31 @@ class LlamaDecoder:
                 d[gk] = torch.ones_like(g)
         self.unit_gains = True
 
+    def _quantise_weights_fp8(self):
+        """weight_dtype="fp8": the model IS the quantised model. Every matmul weight is quantised per
+        output row to e4m3 with a power-of-two scale and the bf16 tensor is replaced by the dequantised
+        values (exact in bf16), so prefill and batched decode compute the same model the batch-1 fp8
+        GEMVs stream at half the bytes. The fp8 copy ({name}_q8 [N, K] e4m3, {name}_s8 [N] fp32) is
+        kept only for the products ops.gemm_w8 accepts; the embedding and the norm gains stay bf16."""
+        o = self.ops
+        prods = [(L, k, e) for L in self.w["layers"]
+                 for k, e in (("wqkv", EPI_NONE), ("wo", EPI_RESID), ("w_gu", EPI_SWIGLU), ("w_down", EPI_RESID))]
+        prods.append((self.w, "lm_head", EPI_NONE))
+        for d, k, epi in prods:
+            w = d[k]
+            q, s = o.quant_weight_fp8_pow2(w)
+            d[k] = (q.float() * s[:, None]).to(w.dtype).contiguous()
+            if o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi):
+                d[k + "_q8"], d[k + "_s8"] = q, s
+            del w, q, s
+
+    def _gemm1(self, d, name, a, **kw):
+        """The product a @ d[name]^T of a decode / prefill layer: the fp8 GEMV when ``a`` is one row
+        and the weight has an fp8 copy (weight_dtype="fp8"), today's bf16 ops.gemm otherwise."""
+        if self.weight_dtype == "fp8" and a.shape[0] == 1 and (name + "_q8") in d:
+            return self.ops.gemm_w8(a, d[name + "_q8"], d[name + "_s8"], **kw)
+        return self.ops.gemm(a, d[name], **kw)
+
     def _gain(self, g):
         """The gain a fused batch-1 GEMV norm streams: none once the gains are folded."""
         return None if self.unit_gains else g
@@ -264,7 +300,7 @@ class LlamaDecoder:
     def _attn_out_and_mlp(self, L, a, x):
         o, tp = self.ops, self.tp
         if tp.size == 1 or tp.rank == 0:
-            o.gemm(a, L["wo"], epi=EPI_RESID, resid=x, out=x)
+            self._gemm1(L, "wo", a, epi=EPI_RESID, resid=x, out=x)
         else:
             o.gemm(a, L["wo"], out=x)
         tp.all_reduce_(x)
@@ -273,12 +309,12 @@ class LlamaDecoder:
     def _mlp(self, L, x):
         o, tp = self.ops, self.tp
         if o.gemv_fusable(x.shape[0], L["w_gu"].shape[0], x.shape[1], EPI_SWIGLU):  # batch 1: norm fused
-            g = o.gemm(x, L["w_gu"], epi=EPI_SWIGLU, rms=(self._gain(L["ln_mlp"]), self.cfg.eps))
+            g = self._gemm1(L, "w_gu", x, epi=EPI_SWIGLU, rms=(self._gain(L["ln_mlp"]), self.cfg.eps))
         else:
             h = o.rmsnorm(x, L["ln_mlp"], self.cfg.eps)
             g = o.gemm(h, L["w_gu"], epi=EPI_SWIGLU)
         if tp.size == 1 or tp.rank == 0:
-            o.gemm(g, L["w_down"], epi=EPI_RESID, resid=x, out=x)
+            self._gemm1(L, "w_down", g, epi=EPI_RESID, resid=x, out=x)
         else:
             o.gemm(g, L["w_down"], out=x)
         tp.all_reduce_(x)
@@ -290,8 +326,8 @@ class LlamaDecoder:
         ``out`` receives it)."""
         o = self.ops
         if o.gemv_fusable(hlast.shape[0], self.w["lm_head"].shape[0], hlast.shape[1]):
-            logits = o.gemm(hlast.contiguous(), self.w["lm_head"], rms=(self._gain(self.w["norm"]), self.cfg.eps),
-                            out=None if gather else out)
+            logits = self._gemm1(self.w, "lm_head", hlast.contiguous(), rms=(self._gain(self.w["norm"]), self.cfg.eps),
+                                 out=None if gather else out)
         else:
             h = o.rmsnorm(hlast, self.w["norm"], self.cfg.eps)
             logits = o.gemm(h, self.w["lm_head"], out=None if gather else out)
@@ -351,7 +387,7 @@ class LlamaDecoder:
         fuse = o.gemv_fusable(x.shape[0], self.w["layers"][0]["wqkv"].shape[0], x.shape[1])
         for li, L in enumerate(self.w["layers"]):
             if fuse:  # batch 1: RMSNorm folded into the QKV GEMV (no separate norm launch)
-                qkv = o.gemm(x, L["wqkv"], out=st.qkv, rms=(self._gain(L["ln_attn"]), c.eps))
+                qkv = self._gemm1(L, "wqkv", x, out=st.qkv, rms=(self._gain(L["ln_attn"]), c.eps))
             else:
                 h = o.rmsnorm(x, L["ln_attn"], c.eps, out=st.h)
                 qkv = o.gemm(h, L["wqkv"], out=st.qkv)

@@ -38,6 +38,8 @@ _SIGS = {
                     + [c_int] * 5 + [c_void_p],
     "da_gemm_fp8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                     c_int, c_int, c_int, c_int, c_void_p],
+    "da_gemv_w8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float,
+                   c_void_p],
     "da_quant_fp8_rows": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "da_layernorm_q": [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p],
     "da_bert_embed_ln_q": [c_void_p] * 11 + [c_int, c_int, c_float, c_void_p],
@@ -402,6 +404,68 @@ def quant_weight_fp8(w: torch.Tensor):
     wf = w.float()
     sw = (wf.abs().amax(dim=1) / 448.0).clamp_min(1e-30)
     return (wf / sw[:, None]).clamp(-448, 448).to(FP8).contiguous(), sw.contiguous()
+
+
+def quant_weight_fp8_pow2(w: torch.Tensor):
+    """Per-output-row e4m3 quantisation with a power-of-two row scale (host-side torch; done once at
+    load): s = the smallest 2^e with amax_row / 2^e <= 448 (all-zero rows: 1). An e4m3 value times a
+    power of two is exact in bf16, so ``q.float() * s[:, None]`` IS a bf16 matrix: the bf16 kernels
+    and the fp8 GEMV compute the same model. Returns (q [N, K] float8_e4m3fn, s [N] fp32)."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    s = torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -100) / 448.0)))
+    s = torch.where(amax / s > 448.0, s * 2, s)        # log2 rounding at an exact power-of-two ratio
+    s = torch.where(amax / (s / 2) <= 448.0, s / 2, s)
+    s = torch.where(amax > 0, s, torch.ones_like(s))
+    return (wf / s[:, None]).clamp(-448, 448).to(FP8).contiguous(), s.contiguous()
+
+
+def gemv_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
+    """True when gemm_w8() accepts the product: the batch-1 GEMV on fp8 weights (csrc/gemv_w8.hip)."""
+    return (M == 1 and K % 1024 == 0 and N % 4 == 0 and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU)
+            and (epi != EPI_SWIGLU or N % 32 == 0))
+
+
+def gemm_w8(a: torch.Tensor, wq: torch.Tensor, sw: torch.Tensor, bias=None, epi: int = EPI_NONE, resid=None,
+            out=None, rms=None) -> torch.Tensor:
+    """out[1, N'] = epi((a[1, K] @ wq[N, K]^T) * sw[None, :]) with e4m3 weights and fp32 row scales
+    (N' = N/2 for EPI_SWIGLU). rms = (gamma or None, eps): RMSNorm(a) fused, as in gemm()."""
+    _bf16_cuda(a, "a")
+    _req(wq.is_cuda and wq.dtype == FP8, f"wq must be float8_e4m3fn on GPU, got {wq.dtype}")
+    _req(a.dim() == 2 and wq.dim() == 2, "gemm_w8 expects 2-D operands")
+    M, K = a.shape
+    N, K2 = wq.shape
+    _req(K == K2, f"K mismatch {K} vs {K2}")
+    _req(gemv_w8_fusable(M, N, K, epi), f"gemm_w8 does not take M={M} N={N} K={K} epi={epi}")
+    _req(a.stride(1) == 1, "a must be a contiguous row")
+    _req(wq.is_contiguous(), "wq must be contiguous")
+    _req(a.data_ptr() % 16 == 0 and wq.data_ptr() % 16 == 0, "operands must be 16-B aligned")
+    _req(sw.is_cuda and sw.dtype == torch.float32 and sw.is_contiguous() and sw.shape == (N,), "sw must be fp32 [N]")
+    nout = N // 2 if epi == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
+    _bf16_cuda(out, "out")
+    _req(out.shape == (M, nout) and out.stride(1) == 1, "bad out")
+    if bias is not None:
+        _bf16_cuda(bias, "bias"); _req(bias.numel() == N and bias.is_contiguous(), "bias must be [N]")
+        _req(epi in (EPI_BIAS, EPI_RESID), "bias only with BIAS/RESID epilogues")
+    if epi == EPI_RESID:
+        _req(resid is not None, "EPI_RESID needs resid")
+        _bf16_cuda(resid, "resid")
+        _req(resid.shape == (M, N) and resid.stride(1) == 1, "bad resid")
+    else:
+        resid = None
+    gamma, eps = (None, 0.0) if rms is None else rms
+    if rms is not None:
+        _req(eps > 0, "fused RMSNorm needs eps > 0")
+        if gamma is not None:
+            _bf16_cuda(gamma, "gamma")
+            _req(gamma.numel() == K and gamma.is_contiguous() and gamma.data_ptr() % 16 == 0, "gamma must be [K]")
+    if N == 0:
+        return out
+    _check(lib().da_gemv_w8(_ptr(a), _ptr(wq), _ptr(sw), _ptr(out), _ptr(bias), _ptr(resid), N, K, epi, _ptr(gamma),
+                            float(eps), _stream()), "gemm_w8")
+    return out
 
 
 def gemm_fp8(aq, sa, wq, sw, bias=None, epi: int = EPI_NONE, resid=None, out=None) -> torch.Tensor:

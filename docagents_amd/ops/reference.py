@@ -472,6 +472,28 @@ def quant_weight_fp8(w):
     return (wf / sw[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), sw.contiguous()
 
 
+def quant_weight_fp8_pow2(w):
+    """kernels.quant_weight_fp8_pow2: e4m3 rows with the smallest power-of-two scale that fits 448."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    s = torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -100) / 448.0)))
+    s = torch.where(amax / s > 448.0, s * 2, s)
+    s = torch.where(amax / (s / 2) <= 448.0, s / 2, s)
+    s = torch.where(amax > 0, s, torch.ones_like(s))
+    return (wf / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), s.contiguous()
+
+
+def gemv_w8_fusable(M, N, K, epi=EPI_NONE):
+    return M == 1 and K % 1024 == 0
+
+
+def gemm_w8(a, wq, sw, bias=None, epi=EPI_NONE, resid=None, out=None, rms=None):
+    if rms is not None:  # as gemm(): the bf16 normalised row
+        g = rms[0] if rms[0] is not None else torch.ones(a.shape[1], dtype=a.dtype, device=a.device)
+        a = rmsnorm(a, g, rms[1])
+    return _epilogue((a.float() @ wq.float().t()) * sw[None, :].float(), wq.shape[0], bias, epi, resid, out)
+
+
 DECODE_DK = True
 # above 32 rows the split-K tiles stay faster (bench/midm_chain.py, profiles/r3/dk/): the narrow
 # dk tiles re-read the activation block once per 16-64 weight rows
