@@ -22,13 +22,18 @@ from docagents_amd.ops import kernels as K  # noqa: E402
 
 def apply_env_overrides() -> dict:
     """Model-level switches read from ``DA_*`` environment variables (one per process):
-    DA_DECODE_DK=0 routes 2..64-row decode GEMMs to the split-K tiles instead of gemm_dk. The kernel
+    DA_DECODE_DK=0 routes 2..64-row decode GEMMs to the split-K tiles instead of gemm_dk;
+    DA_PREFILL_TAIL=0 runs every prefill row through the last layer (profiles/tailcut/). The kernel
     schedule setters and the rejected decode / prefill arms of rounds 1-4 were removed from the
     library (git history keeps them; profiles/r4/rejected_r4.txt has their numbers)."""
     done = {}
     if os.environ.get("DA_DECODE_DK") is not None:  # decode GEMMs: gemm_dk (1) vs split-K tiles (0)
         K.DECODE_DK = os.environ["DA_DECODE_DK"] != "0"
         done["DA_DECODE_DK"] = int(K.DECODE_DK)
+    if os.environ.get("DA_PREFILL_TAIL") is not None:  # prefill: last layer on the read rows only (1) / all rows (0)
+        from docagents_amd.models import llama
+        llama._PREFILL_TAIL = os.environ["DA_PREFILL_TAIL"] != "0"  # (the module reads it itself on import)
+        done["DA_PREFILL_TAIL"] = int(llama._PREFILL_TAIL)
     return done
 
 

@@ -23,6 +23,8 @@ in-place all-reduce yields x + sum of partials.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -34,6 +36,10 @@ EPI_NONE, EPI_SWIGLU, EPI_RESID, EPI_ROPE = 0, 3, 4, 6
 # Decode step of MHA models: RoPE + KV-cache write folded into the attention kernel (False: separate
 # rope_cache launch; the GPU tests compare both).
 _FUSED_ROPE_DECODE = True
+# Prefill: the last layer's attention, O projection and MLP run only on the rows whose logits are
+# read (one per sequence); its K / V cache writes still cover every token (DA_PREFILL_TAIL=0: every
+# row through the whole layer; the tests compare both, bit for bit).
+_PREFILL_TAIL = os.environ.get("DA_PREFILL_TAIL", "1") != "0"
 
 
 class TPContext:
@@ -320,6 +326,33 @@ class LlamaDecoder:
         tp.all_reduce_(x)
         return x
 
+    def _tail_routes(self, M: int):
+        """The gemm() routings (ops.gemm_route) of the last layer's O, gate/up and down products in a
+        prefill over M rows, or None where the prefill runs every row through that layer (flag off;
+        M so small that the products are not on the prefill tiles)."""
+        if not _PREFILL_TAIL:
+            return None
+        L = self.w["layers"][-1]
+        prods = (("wo", EPI_RESID), ("w_gu", EPI_SWIGLU), ("w_down", EPI_RESID))
+        routes = [self.ops.gemm_route(M, L[k].shape[0], L[k].shape[1], e) for k, e in prods]
+        return None if any(r is None for r in routes) else routes
+
+    def _attn_out_and_mlp_rows(self, L, a, x, routes, M: int):
+        """_attn_out_and_mlp for rows gathered from a prefill over M rows: every product and the norm
+        run the kernel (tile, K order, split count) the M-row pass would, so each row ends with the
+        bits that pass gives it. The fused-norm GEMV that _mlp takes for a single row is not used."""
+        o, tp = self.ops, self.tp
+        first = tp.size == 1 or tp.rank == 0  # the residual is added by one rank's epilogue only
+        res = dict(epi=EPI_RESID, resid=x) if first else {}
+        r_o, r_gu, r_down = routes
+        o.gemm(a, L["wo"], out=x, **res, **r_o)
+        tp.all_reduce_(x)
+        h = o.rmsnorm(x, L["ln_mlp"], self.cfg.eps, route_m=M)
+        g = o.gemm(h, L["w_gu"], epi=EPI_SWIGLU, **r_gu)
+        o.gemm(g, L["w_down"], out=x, **res, **r_down)
+        tp.all_reduce_(x)
+        return x
+
     def _logits(self, hlast, gather: bool = True, out=None):
         """Logits of the rows of ``hlast``: the full [B, V] (gather=True; an all-gather of the vocab
         slices under TP) or this rank's slice [B, V/t] (gather=False: what ``sample`` consumes;
@@ -354,6 +387,10 @@ class LlamaDecoder:
         x = o.embed(ids, self.w["embed"])
         hook = self.layer_hook
         kv_from_cache = bool(getattr(o, "flash_kv_cache_ok", lambda *_: False)(D, True))
+        M, last = x.shape[0], len(self.w["layers"]) - 1
+        # the last layer's hidden rows are read at last_idx only (its K / V rows by decode, from the
+        # cache): past its QKV projection it runs on those rows alone, with the full pass's bits
+        tail = self._tail_routes(M)
         for li, L in enumerate(self.w["layers"]):
             if hook is not None:  # e.g. move the rest of a prefill to another (CU-masked) stream
                 hook(li)
@@ -363,13 +400,18 @@ class LlamaDecoder:
             qkv = o.gemm_rope(h, L["wqkv"], pos, self.cos_sin, hl, kl, D, slot_tok, cache.k(li), cache.v(li),
                               kv_out=not kv_from_cache)
             pre = None if prefix is None else (cache.k(li)[prefix[0]], cache.v(li)[prefix[0]], prefix[1])
+            cut = tail is not None and li == last
             if kv_from_cache:
                 a = o.flash_attn_varlen(qkv[:, :hl * D], None, None, cu, max_seqlen, hl, kl, D, causal=True,
-                                        prefix=pre, kv_cache=(cache.k(li), cache.v(li), slot_tok, pos))
+                                        prefix=pre, kv_cache=(cache.k(li), cache.v(li), slot_tok, pos),
+                                        tail_only=cut)
             else:
                 a = o.flash_attn_varlen(qkv[:, :hl * D], qkv[:, hl * D:(hl + kl) * D], qkv[:, (hl + kl) * D:], cu,
-                                        max_seqlen, hl, kl, D, causal=True, prefix=pre)
+                                        max_seqlen, hl, kl, D, causal=True, prefix=pre, tail_only=cut)
             del qkv, h
+            if cut:
+                x = self._attn_out_and_mlp_rows(L, a.index_select(0, last_idx), x.index_select(0, last_idx), tail, M)
+                return self._logits(x, gather=not local_logits)
             x = self._attn_out_and_mlp(L, a, x)
         return self._logits(x.index_select(0, last_idx), gather=not local_logits)
 

@@ -63,6 +63,10 @@ struct FaPrefix {
   const bf16_t* kc;
   const bf16_t* vc;
   long long slot_stride;
+  // tail mode (grid x = 1): each (sequence, head) computes and stores only the query block that
+  // holds the sequence's last token, exactly as the full launch computes that block (same q0, key
+  // range, tiles, code path: the same bits); every other row of o is left unwritten
+  int tail;
 };
 
 // The (query block, head, sequence) a flash workgroup works on, from its place in the dispatch
@@ -91,6 +95,13 @@ __device__ __forceinline__ FaBlock fa_block(int rev, int causal, int G) {
   return FaBlock{lpt ? X - 1 - (int)blockIdx.x : (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
 }
 
+// The query block a workgroup runs: its place in the dispatch order, or in tail mode the block (of
+// QB rows) that holds the last token of its sequence (L tokens; the grid is one block wide, so
+// fa_block's XCD grouping sees per = G workgroups per pair and its longest-first order one block).
+__device__ __forceinline__ int fa_query_block(const FaBlock& fb, int tail, int L, int QB) {
+  return tail ? (L > 0 ? (L - 1) / QB : 0) : fb.qb;
+}
+
 // QH = 32-query halves per wave. QH = 2: each K fragment read from LDS feeds the S MFMAs of both
 // halves and each transposed V fragment the O MFMAs of both, so LDS read bytes per FLOP halve (at
 // QH = 1 the LDS reads of a tile take as long as its MFMAs); the two halves' softmax VALU work is
@@ -106,8 +117,9 @@ flash_attn_v2_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const FaBlock fb = fa_block(pre.rev, causal, H / Hkv);  // dispatch order: see fa_block
-  const int b = fb.b, h = fb.h, qb = fb.qb;
+  const int b = fb.b, h = fb.h;
   const int s0 = cu[b], L = cu[b + 1] - s0;
+  const int qb = fa_query_block(fb, pre.tail, L, C::QB);
   const int q0 = qb * C::QB;
   if (q0 >= L) return;
   const int hk = h / (H / Hkv);
@@ -421,8 +433,9 @@ flash_attn_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ 
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const FaBlock fb = fa_block(pre.rev, causal, H / Hkv);  // dispatch order: see fa_block
-  const int b = fb.b, h = fb.h, qb = fb.qb;
+  const int b = fb.b, h = fb.h;
   const int s0 = cu[b], L = cu[b + 1] - s0;
+  const int qb = fa_query_block(fb, pre.tail, L, C::QB);
   const int q0 = qb * C::QB;
   if (q0 >= L) return;
   const int hk = h / (H / Hkv);
@@ -1826,7 +1839,7 @@ static int launch_fa2(const void* q, const void* k, const void* v, int ldq, int 
       attr_set = true;
     }
   }
-  dim3 grid((max_seqlen + 32 * QH * NW - 1) / (32 * QH * NW), H, B);
+  dim3 grid(pre.tail ? 1 : (max_seqlen + 32 * QH * NW - 1) / (32 * QH * NW), H, B);
 #define FA_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, (const int*)cu_seqlens, H, Hkv, \
                 causal, sl2e, (bf16_t*)o, ldo, pre
   switch (D) {
@@ -1868,7 +1881,7 @@ static int launch_fa_pipe(const void* q, const void* k, const void* v, int ldq, 
                               hipFuncAttributeMaxDynamicSharedMemorySize, fa_pipe_smem<96, DMA>());
     attr_set = true;
   }
-  dim3 grid((max_seqlen + 127) / 128, H, B);
+  dim3 grid(pre.tail ? 1 : (max_seqlen + 127) / 128, H, B);
   flash_attn_pipe_kernel<96, true, DMA><<<grid, 256, fa_pipe_smem<96, DMA>(), s>>>(
       (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, (const int*)cu_seqlens, H, Hkv, causal, sl2e,
       (bf16_t*)o, ldo, pre);
@@ -1880,11 +1893,14 @@ static int launch_fa_pipe(const void* q, const void* k, const void* v, int ldq, 
 // kv_slot / kv_pos (nullable; per token, int32): the sequences' own keys are read from the KV cache
 // k_cache / v_cache [slots, Hkv, max_seq, D] (pre_hstride = max_seq * D) instead of k / v — causal
 // D = 96 only.
+// tail_only: per (sequence, head) only the query block holding the sequence's last token is computed
+// and stored (128 rows; 256 on the 8-wave D = 128 kernel), bit-identical to the full launch's rows;
+// the other rows of o are not written. Both the pipelined and the flash_attn_v2 kernels take it.
 DA_EXPORT int da_flash_attn_v2(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                                const void* cu_seqlens, int B, int max_seqlen, int H, int Hkv, int D, int causal,
                                float scale, void* o, int ldo, const void* pre_k, const void* pre_v,
                                long long pre_hstride, int pre_len, const void* kv_slot, const void* kv_pos,
-                               const void* k_cache, const void* v_cache, void* stream) {
+                               const void* k_cache, const void* v_cache, int tail_only, void* stream) {
   const bool from_cache = kv_slot != nullptr;
   if (from_cache) {
     if (!causal || D != 96 || !kv_pos || !k_cache || !v_cache || pre_hstride < (long long)D ||
@@ -1900,7 +1916,7 @@ DA_EXPORT int da_flash_attn_v2(const void* q, const void* k, const void* v, int 
   hipStream_t s = (hipStream_t)stream;
   const FaPrefix pre{(const bf16_t*)pre_k, (const bf16_t*)pre_v, pre_hstride, pre_len, kFaDispatch,
                      (const int*)kv_slot, (const int*)kv_pos, (const bf16_t*)k_cache, (const bf16_t*)v_cache,
-                     from_cache ? (long long)Hkv * pre_hstride : 0LL};
+                     from_cache ? (long long)Hkv * pre_hstride : 0LL, tail_only ? 1 : 0};
   if (causal && D == 96) {
     const bool dma = pre_len % 64 == 0 && ((uintptr_t)k | (uintptr_t)v | (uintptr_t)pre_k | (uintptr_t)pre_v) % 16 == 0;
     if (dma) return launch_fa_pipe<true>(q, k, v, ldq, ldk, ldv, cu_seqlens, B, max_seqlen, H, Hkv, causal, sl2e, o, ldo, pre, s);

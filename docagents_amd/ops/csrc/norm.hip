@@ -368,12 +368,15 @@ static inline int row_threads(int D) {
 }
 static inline bool d_ok(int D) { return D % 8 == 0 && D / 8 <= MAXCH * 256; }
 
-DA_EXPORT int da_rmsnorm(const void* x, int ldx, void* resid, const void* w, void* y, int ldy, int M, int D,
-                         float eps, void* stream) {
+// route_m: the row count the kernel is chosen for (M rows are normalised). The two kernels sum a
+// row's squares in different orders, so a caller that normalises a subset of a pass's rows and wants
+// the bits that pass gives them passes the pass's row count (da_rmsnorm_routed); da_rmsnorm: M.
+static int rmsnorm_launch(const void* x, int ldx, void* resid, const void* w, void* y, int ldy, int M, int D,
+                          float eps, int route_m, void* stream) {
   if (!d_ok(D) || ldx % 8 || ldy % 8) return (int)hipErrorInvalidValue;
   if (M == 0) return 0;
   // many rows of a width that is whole 512-element wave slices: one wave per row
-  if (M >= 1024 && D % 512 == 0 && D / 512 <= 8) {
+  if (route_m >= 1024 && D % 512 == 0 && D / 512 <= 8) {
     const dim3 grid((M + 3) / 4);
 #define RMS_ROWS(N) rmsnorm_rows_kernel<N><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x, (bf16_t*)resid, \
                       (const bf16_t*)w, (bf16_t*)y, M, D, eps, ldx, ldy)
@@ -391,6 +394,16 @@ DA_EXPORT int da_rmsnorm(const void* x, int ldx, void* resid, const void* w, voi
   rmsnorm_kernel<<<M, row_threads(D), 0, (hipStream_t)stream>>>((const bf16_t*)x, (bf16_t*)resid,
                                                                  (const bf16_t*)w, (bf16_t*)y, D, eps, ldx, ldy);
   DA_LAUNCH_CHECK();
+}
+
+DA_EXPORT int da_rmsnorm(const void* x, int ldx, void* resid, const void* w, void* y, int ldy, int M, int D,
+                         float eps, void* stream) {
+  return rmsnorm_launch(x, ldx, resid, w, y, ldy, M, D, eps, M, stream);
+}
+
+DA_EXPORT int da_rmsnorm_routed(const void* x, int ldx, void* resid, const void* w, void* y, int ldy, int M, int D,
+                                float eps, int route_m, void* stream) {
+  return rmsnorm_launch(x, ldx, resid, w, y, ldy, M, D, eps, route_m < M ? M : route_m, stream);
 }
 
 DA_EXPORT int da_layernorm(const void* x, const void* resid, const void* g, const void* b, void* y, int M, int D,

@@ -46,6 +46,8 @@ _SIGS = {
     "da_gemm_resid_rmsnorm": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                               c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p],
     "da_rmsnorm": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
+    "da_rmsnorm_routed": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                          c_void_p],
     "da_swiglu_interleaved": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     "da_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "da_bert_embed_ln": [c_void_p] * 9 + [c_int, c_int, c_float, c_void_p],
@@ -56,7 +58,8 @@ _SIGS = {
                  + [c_int] * 5 + [c_void_p],
     "da_flash_attn_v2": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
                          c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_longlong,
-                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "da_gemm_route": [c_int, c_int, c_int, c_int],
     "da_malloc_uncached": [c_longlong, ctypes.POINTER(c_void_p)],
     "da_gemm_dk": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                    c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
@@ -262,6 +265,25 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_NONE, resid
                             M, N, K, epi, tile, splits, _ptr(ws), _ptr(gamma), float(eps), _stream())
     _check(rc, "gemm")
     return out
+
+
+def gemm_route(M: int, N: int, K: int, epi: int = EPI_NONE):
+    """The prefill routing of gemm() at M rows, as keywords for gemm(): {"tile": t, "splits": s}.
+    A product over a subset of those rows run with them (gemm(a[idx], w, **gemm_route(M, N, K, epi)))
+    goes through the same tile kernel with the same K order and split count as the full launch, so
+    each row gets the bits the full launch gives it (GEMM rows are independent; the persistent and
+    the one-tile-per-workgroup forms of gemm8p are bit-identical). None for M <= 128: those go to
+    the GEMV / gemm_dk / weight-streaming family, chosen by more than the tile number."""
+    if M <= 128:
+        return None
+    if M < 640:
+        tile = _decode_tile(M, N)
+        splits = _auto_splits(M, N, K)
+    else:
+        tile, splits = 0, 1
+    if tile == 0:
+        tile = int(lib().da_gemm_route(M, N, K, splits))
+    return {"tile": tile, "splits": splits}
 
 
 # Decode GEMMs with 2..64 rows: gemm_dk (csrc/gemm_dk.hip: K split across the 4 waves of a
@@ -563,7 +585,9 @@ def _auto_splits(M: int, N: int, K: int) -> int:
 
 
 # ------------------------------------------------------------------------------ norms etc.
-def rmsnorm(x, w, eps: float, resid=None, out=None):
+def rmsnorm(x, w, eps: float, resid=None, out=None, route_m: int = 0):
+    """route_m > M: run the kernel a pass over route_m rows would take (the many-row kernel sums a
+    row's squares in another order), so a subset of that pass's rows gets the pass's bits."""
     _bf16_cuda(x, "x"); _bf16_cuda(w, "w")
     M, D = x.shape
     _req(x.stride(1) == 1 and x.stride(0) % 8 == 0 and D % 8 == 0, "x must be row-major, D % 8 == 0")
@@ -573,8 +597,8 @@ def rmsnorm(x, w, eps: float, resid=None, out=None):
     if out is None:
         out = torch.empty((M, D), dtype=torch.bfloat16, device=x.device)
     _req(out.stride(1) == 1 and out.stride(0) % 8 == 0, "bad out")
-    _check(lib().da_rmsnorm(_ptr(x), x.stride(0), _ptr(resid), _ptr(w), _ptr(out), out.stride(0), M, D,
-                            float(eps), _stream()), "rmsnorm")
+    _check(lib().da_rmsnorm_routed(_ptr(x), x.stride(0), _ptr(resid), _ptr(w), _ptr(out), out.stride(0), M, D,
+                                   float(eps), int(route_m), _stream()), "rmsnorm")
     return out
 
 
@@ -665,13 +689,16 @@ def flash_kv_cache_ok(D: int, causal: bool) -> bool:
 
 
 def flash_attn_varlen(q, k, v, cu_seqlens, max_seqlen: int, H: int, Hkv: int, D: int, causal: bool,
-                      scale: float | None = None, out=None, prefix=None, kv_cache=None):
+                      scale: float | None = None, out=None, prefix=None, kv_cache=None, tail_only: bool = False):
     """q/k/v: 2-D [T, *] views with head h at columns h*D (strided views into a packed qkv are fine).
     prefix = (k_pre, v_pre, P): shared-prefix keys of every sequence, one KV-cache slot's
     [Hkv, max_seq, D] K and V (RoPE applied); query i of a sequence is key P + i.
     kv_cache = (k_cache, v_cache, slot, pos) (flash_kv_cache_ok only): the own keys of the sequence
     starting at token t are k_cache[slot[t], :, pos[t] + j] (slot / pos int32 per token, as the QKV
-    projection wrote them); k / v are then ignored (None allowed)."""
+    projection wrote them); k / v are then ignored (None allowed).
+    tail_only: per (sequence, head) only the query block that holds the sequence's last token is
+    computed and stored (one workgroup; the same bits as a full launch gives those rows); every other
+    row of ``out`` is left as it was."""
     kc = vc = ks = kpos = None
     if kv_cache is not None:
         kc, vc, ks, kpos = kv_cache
@@ -707,7 +734,7 @@ def flash_attn_varlen(q, k, v, cu_seqlens, max_seqlen: int, H: int, Hkv: int, D:
     _check(lib().da_flash_attn_v2(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0),
                                   _ptr(cu_seqlens), B, int(max_seqlen), H, Hkv, D, int(causal), float(scale),
                                   _ptr(out), out.stride(0), _ptr(kp), _ptr(vp), hstride, P, _ptr(ks), _ptr(kpos),
-                                  _ptr(kc), _ptr(vc), _stream()),
+                                  _ptr(kc), _ptr(vc), int(bool(tail_only)), _stream()),
            "flash_attn_varlen")
     return out
 

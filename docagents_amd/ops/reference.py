@@ -20,6 +20,12 @@ def gemv_fusable(M, N, K, epi=EPI_NONE):
     return M == 1
 
 
+def gemm_route(M, N, K, epi=EPI_NONE):
+    """kernels.gemm_route: gemm() keywords that give a subset of M rows the full launch's routing
+    (none needed here: the oracle has one routine), None for M <= 128 as there."""
+    return None if M <= 128 else {}
+
+
 def gemm(a, w, bias=None, epi=EPI_NONE, resid=None, out=None, rms=None, **_):
     if rms is not None:  # same numerics as rmsnorm() followed by gemm() (bf16 normalised row)
         g = rms[0] if rms[0] is not None else torch.ones(a.shape[1], dtype=a.dtype, device=a.device)
@@ -70,7 +76,7 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     return torch.stack([g, u], dim=1).reshape(2 * Fd, K).contiguous()
 
 
-def rmsnorm(x, w, eps, resid=None, out=None):
+def rmsnorm(x, w, eps, resid=None, out=None, route_m=0):
     xf = x.float()
     if resid is not None:
         xf = xf + resid.float()
@@ -170,11 +176,14 @@ def flash_kv_cache_ok(D: int, causal: bool) -> bool:
 
 
 def flash_attn_varlen(q, k, v, cu_seqlens, max_seqlen, H, Hkv, D, causal, scale=None, out=None, prefix=None,
-                      kv_cache=None):
+                      kv_cache=None, tail_only=False):
     """prefix = (k_pre [Hkv, >=P, D], v_pre, P): every sequence's keys are the P shared prefix keys
     followed by its own; query i sits at key position P + i (bottom-right causal).
     kv_cache = (k_cache, v_cache, slot, pos): own keys of the sequence starting at token t read from
-    k_cache[slot[t], :, pos[t] + j] (k / v ignored)."""
+    k_cache[slot[t], :, pos[t] + j] (k / v ignored).
+    tail_only: only the 128-row query block holding each sequence's last token is defined (computed
+    as in a full call, so the same bits); the other rows, which the kernel leaves unwritten, are NaN
+    here so that a consumer of one shows up."""
     if kv_cache is not None:
         kc, vc, ks, kpos = kv_cache
         T = q.shape[0]
@@ -212,6 +221,8 @@ def flash_attn_varlen(q, k, v, cu_seqlens, max_seqlen, H, Hkv, D, causal, scale=
             s = s.masked_fill(m, float("-inf"))
         p = s.softmax(-1)
         res[s0:s1] = (p @ vv).transpose(0, 1).reshape(L, H * D).to(q.dtype)
+        if tail_only:
+            res[s0:s0 + (L - 1) // 128 * 128] = float("nan")
     if out is not None:
         out.copy_(res)
         return out
