@@ -310,6 +310,7 @@ def test_decode_attn_fused_rope(D, lens, chunk):
     slot = torch.arange(B, dtype=torch.int32, device=DEV) + 1
     cs = R.rope_table(max_seq, D, 10000.0, device=DEV)
     kc2, vc2, qkv2, qkv0 = kc.clone(), vc.clone(), qkv.clone(), qkv.clone()
+    kc0, vc0 = kc.clone(), vc.clone()
     K.rope_cache(qkv2, pos, cs, H, H, D, slot=slot, k_cache=kc2, v_cache=vc2)
     want = K.decode_attn(qkv2, kc2, vc2, L, slot, H, H, D, max_seq, chunk=chunk)
     got = K.decode_attn(qkv, kc, vc, L, slot, H, H, D, max_seq, chunk=chunk, rope=(cs, pos))
@@ -319,6 +320,10 @@ def test_decode_attn_fused_rope(D, lens, chunk):
         _close(kc[s_, :, p_], kc2[s_, :, p_], atol=0.01)
         assert torch.equal(vc[s_, :, p_], vc2[s_, :, p_])
     assert torch.equal(qkv, qkv0)  # q / k rows untouched (the kernel rotates on the fly)
+    rest = torch.ones(slots, max_seq, dtype=torch.bool, device=DEV)
+    rest[slot.long(), pos.long()] = False  # every cache row but the B written ones keeps its bits
+    assert torch.equal(kc.transpose(1, 2)[rest], kc0.transpose(1, 2)[rest])
+    assert torch.equal(vc.transpose(1, 2)[rest], vc0.transpose(1, 2)[rest])
     ref = R.decode_attn(qkv.clone(), kc.clone(), vc.clone(), L, slot, H, H, D, rope=(cs, pos))
     _close(got, ref, atol=0.02)
 
