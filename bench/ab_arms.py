@@ -18,6 +18,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from docagents_amd.ops import gemm_plan  # noqa: E402
 from docagents_amd.ops import kernels as K  # noqa: E402
 
 def apply_env_overrides() -> dict:
@@ -28,8 +29,8 @@ def apply_env_overrides() -> dict:
     library (git history keeps them; profiles/r4/rejected_r4.txt has their numbers)."""
     done = {}
     if os.environ.get("DA_DECODE_DK") is not None:  # decode GEMMs: gemm_dk (1) vs split-K tiles (0)
-        K.DECODE_DK = os.environ["DA_DECODE_DK"] != "0"
-        done["DA_DECODE_DK"] = int(K.DECODE_DK)
+        gemm_plan.DECODE_DK = os.environ["DA_DECODE_DK"] != "0"  # (plan()'s cache is keyed on it)
+        done["DA_DECODE_DK"] = int(gemm_plan.DECODE_DK)
     if os.environ.get("DA_PREFILL_TAIL") is not None:  # prefill: last layer on the read rows only (1) / all rows (0)
         from docagents_amd.models import llama
         llama._PREFILL_TAIL = os.environ["DA_PREFILL_TAIL"] != "0"  # (the module reads it itself on import)

@@ -14,6 +14,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from docagents_amd.ops import gemm_plan  # noqa: E402
 from docagents_amd.ops import kernels as K  # noqa: E402
 
 SHAPES = {
@@ -71,8 +72,9 @@ def main():
                                    splits=splits)
                     return run
                 res = {}
-                auto_s = K._auto_splits(M, N, Kd)
-                tiles = [K._decode_tile(M)] if a.tiles == "auto" else [int(t) for t in a.tiles.split(",")]
+                auto = gemm_plan.plan_resid_norm(M, N, Kd)  # the split-K decode tile and split count at M rows
+                auto_s = auto.splits
+                tiles = [auto.tile] if a.tiles == "auto" else [int(t) for t in a.tiles.split(",")]
                 for tile in tiles:
                     if kind == "norm" and M > 64 and tile != 9:
                         continue  # the fused reduce + norm runs on the 128x64 tile above 64 rows

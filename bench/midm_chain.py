@@ -11,6 +11,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from docagents_amd.ops import gemm_plan  # noqa: E402
 from docagents_amd.ops import kernels as K  # noqa: E402
 from ab_arms import apply_env_overrides, swiglu_interleaved  # noqa: E402
 apply_env_overrides()  # DA_* schedule overrides for A/B sweeps (DA_GEMM_DB, DA_GEMM_PF, ...)
@@ -52,7 +53,7 @@ def main():
                         else:
                             t, s = (int(v) for v in arm.split(":"))
                             if s == 0:
-                                s = K._auto_splits(max(M, 1), w.shape[0], w.shape[1])
+                                s = gemm_plan.auto_splits(max(M, 1), w.shape[0], w.shape[1])
                             if j == 2:
                                 K.gemm(xi, w, epi=K.EPI_SWIGLU, out=act, tile=t, splits=s)
                             else:

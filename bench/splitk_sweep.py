@@ -1,4 +1,4 @@
-"""Decode-sized (M = 64) GEMM: tile x split-K sweep (sets _auto_splits). Weights are cycled through
+"""Decode-sized (M = 64) GEMM: tile x split-K sweep (sets gemm_plan.auto_splits). Weights are cycled through
 enough copies (>= 1 GiB) that every call streams them cold from HBM, as in a real decode step
 (each layer's weights are read once per step; 7.6 GB/step for Phi-3 >> the 256 MB MALL)."""
 import os
@@ -7,7 +7,10 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from docagents_amd.ops import gemm_plan  # noqa: E402
 from docagents_amd.ops import kernels as K  # noqa: E402
+
+CUS = torch.cuda.get_device_properties(0).multi_processor_count
 
 
 def t(fn, it=50):
@@ -37,7 +40,8 @@ for name, M, N, Kd, epi in [("qkv", 64, 9216, 3072, 0), ("o", 64, 3072, 3072, 4)
     def nxt():
         it[0] = (it[0] + 1) % ncopy
         return ws[it[0]]
-    out = [f"auto(s={K._auto_splits(M, N, Kd)})={t(lambda: K.gemm(x, nxt(), epi=epi, resid=r)) * 1e3:.1f}"]
+    auto = gemm_plan.plan(M, N, Kd, epi, cus=CUS)
+    out = [f"auto({auto.family} t{auto.tile} s={auto.splits})={t(lambda: K.gemm(x, nxt(), epi=epi, resid=r)) * 1e3:.1f}"]
     for tile in (2, 3):
         for s in (1, 2, 4, 8, 16, 32):
             if (Kd // 64) % s:

@@ -628,32 +628,12 @@ DA_EXPORT int da_gemm_rope(const void* A, int lda, const void* W, void* C, int l
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.k_per_split = K;
   a.rope = RopeArgs{(const int*)pos, (const int*)slot, (const float*)cos_sin, (bf16_t*)k_cache, (bf16_t*)v_cache,
                     H, Hkv, D, max_seq, kv_out ? 1 : 0};
+  // its own measured rule for the RoPE epilogue, not ops/gemm_plan.py's prefill_bm
   const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
   return launch_gemm8p(a, EPI_ROPE, (hipStream_t)stream, t256 >= 256 ? 256 : 128);
 }
 
-// Tile selection: big tiles when the grid fills 256 CUs, skinny tiles (+ split-K) for decode-sized M.
-// tile: 0 = auto, 1 = 128x128, 2 = 64x128, 3 = 32x128, 4 / 7 = 256x256 phase-split (gemm8p),
-// 6 = GEMV (M = 1), 8 = 128x128 PF4, 9 = 128x64 PF4, 10 = 128x256 phase-split (gemm8p),
-// 13 = 256x256 four-wave (gemm4w).
-static int auto_tile(int M, int N, int K, int splits) {
-  // decode-sized M: 32x128 / 64x128 weight-streaming tiles (+ split-K, chosen by the caller);
-  // 65..639 rows: the 64x128 tile over ceil(M/64) row blocks; from 640 rows the phase-split
-  // kernel with the row-tile height of fewer workgroup waves (gemm8p_pick_bm; 32-layer Phi-3
-  // chain and single-GEMM sweeps: bench/midm_chain.py, bench/gemm_ab.py, profiles/r2, r3)
-  if (M <= 32) return 3;
-  if (M < 640 || splits > 1) return 2;
-  if (K < 128) return 1;
-  return gemm8p_pick_bm(M, N) == 256 ? 7 : 10;
-}
-
-// The tile da_gemm_bf16 runs for tile = 0 at this shape (no launch). A caller that computes a
-// subset of a product's rows passes it back as tile=: rows are independent, so the same tile kernel
-// with the same K order (and split count) gives each row the bits the full-M launch gives it.
-DA_EXPORT int da_gemm_route(int M, int N, int K, int splits) {
-  return auto_tile(M, N, K, splits < 1 ? 1 : splits);
-}
-
+// tile / splits: chosen by ops/gemm_plan.py (the tile ids' legend is there); tile 0 is an error.
 DA_EXPORT int da_gemm_bf16(const void* A, int lda, const void* W, void* C, int ldc,
                            const void* bias, const void* resid, int ldr,
                            int M, int N, int K, int epi, int tile, int splits, void* ws,
@@ -670,7 +650,6 @@ DA_EXPORT int da_gemm_bf16(const void* A, int lda, const void* W, void* C, int l
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.k_per_split = K / splits;
   a.gamma = (const bf16_t*)rms_gamma; a.eps = rms_eps;
   if ((rms_gamma || rms_eps > 0.f) && tile != 6) return (int)hipErrorInvalidValue;  // fused RMSNorm: GEMV only
-  if (tile == 0) tile = auto_tile(M, N, K, splits);
   if (tile == 4 || tile == 7 || tile == 10) {
     if (splits != 1 || K < 128) return (int)hipErrorInvalidValue;
     return launch_gemm8p(a, epi, s, tile == 10 ? 128 : 256);

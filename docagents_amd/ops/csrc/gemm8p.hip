@@ -535,21 +535,6 @@ static int launch8p(const GemmArgs& a0, int epi, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// Row-tile height for a non-RoPE prefill product: the one with fewer workgroup WAVES over the
-// chip's CUs, weighting a 128-row tile's time as 0.72 of a 256-row one (measured at M = 2930:
-// 128-row tiles took 0.61-0.73 of the 256-row tile time, profiles/r3/gemm_ab_batch1_prefill_tiles.txt).
-// At M ~ 2.6k (the batch-1 prefill of the p50 path) the O / down projections (N = 3072) then run
-// 252 128-row tiles in one wave instead of 132 256-row tiles on half the chip; QA-sized chunks
-// (M ~ 64k) keep 256 (the round-3 rule, 256 rows once the 256-row grid reached half the chip,
-// measured 65.5 vs 74.9 us per O projection at M ~ 2.6k: profiles/r4/bm_rule/).
-int gemm8p_pick_bm(int M, int N) {
-  const long ntn = (N + 255) / 256;
-  const long t256 = (long)((M + 255) / 256) * ntn, t128 = (long)((M + 127) / 128) * ntn;
-  const int cus = num_cus();
-  const long w256 = (t256 + cus - 1) / cus, w128 = (t128 + cus - 1) / cus;
-  return w128 * 72 < w256 * 100 ? 128 : 256;
-}
-
 // epi + 100: the same kernel on fp16 operands / output (v_mfma_f32_16x16x32_f16)
 int launch_gemm8p(const GemmArgs& a, int epi, hipStream_t s, int bm) {
   if (a.K < 128 || a.K % 64) return (int)hipErrorInvalidValue;
@@ -560,15 +545,16 @@ int launch_gemm8p(const GemmArgs& a, int epi, hipStream_t s, int bm) {
 
 // fp16 GEMM for the encoder's DTYPE=fp16 path: C = epi(A W^T), A [M, K] / W [N, K] / C / bias /
 // resid fp16, fp32 accumulation; epi NONE / BIAS / GELU / RESID. Every M on the phase-split tile
-// (128-row tiles below half a chip of 256-row ones): the fp16 path has no decode-sized tiles.
+// of bm = 128 or 256 rows (ops/gemm_plan.py prefill_bm): the fp16 path has no decode-sized tiles.
 DA_EXPORT int da_gemm_f16(const void* A, int lda, const void* W, void* C, int ldc, const void* bias,
-                          const void* resid, int ldr, int M, int N, int K, int epi, void* stream) {
+                          const void* resid, int ldr, int M, int N, int K, int epi, int bm, void* stream) {
   if (M < 1 || K % 64 || K < 128 || N % 8 || lda % 8 || ldc % 8) return (int)hipErrorInvalidValue;
+  if (bm != 128 && bm != 256) return (int)hipErrorInvalidValue;
   if (epi != EPI_NONE && epi != EPI_BIAS && epi != EPI_GELU && epi != EPI_RESID) return (int)hipErrorInvalidValue;
   if (epi == EPI_RESID && (!resid || ldr % 8)) return (int)hipErrorInvalidValue;
   GemmArgs a{};
   a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C;
   a.bias = (const bf16_t*)bias; a.resid = (const bf16_t*)resid;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.k_per_split = K;
-  return launch_gemm8p(a, 100 + epi, (hipStream_t)stream, gemm8p_pick_bm(M, N));
+  return launch_gemm8p(a, 100 + epi, (hipStream_t)stream, bm);
 }

@@ -17,6 +17,10 @@ from pathlib import Path
 
 import torch
 
+from . import gemm_plan
+from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, gemv_fusable,  # noqa: F401 - re-exported
+                        gemv_w8_fusable)
+
 _LIB = None
 _LOCK = threading.Lock()
 # DA_KERNELS_DEBUG=1: the -DDA_DEBUG build (device asserts: bounds / shape preconditions inside the
@@ -59,7 +63,6 @@ _SIGS = {
     "da_flash_attn_v2": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
                          c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_longlong,
                          c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "da_gemm_route": [c_int, c_int, c_int, c_int],
     "da_malloc_uncached": [c_longlong, ctypes.POINTER(c_void_p)],
     "da_gemm_dk": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                    c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
@@ -90,7 +93,7 @@ _SIGS = {
     "da_gemm8p_persist": [c_int],
     "da_gemm4w_variant": [c_int],
     "da_gemm_f16": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                    c_void_p],
+                    c_int, c_void_p],
     "da_flash_attn_f16": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_float, c_void_p, c_int, c_void_p],
     "da_layernorm_f16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
@@ -206,9 +209,16 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
-def gemv_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
-    """True when gemm() runs the batch-1 GEMV (which can also fuse the input RMSNorm)."""
-    return M == 1 and K % 512 == 0 and N % 4 == 0 and (epi != EPI_SWIGLU or N % 32 == 0)
+_CUS = {}
+
+
+def _cus(device=None) -> int:
+    """CU count of ``device`` (default: the current one), read once per device: gemm_plan's input."""
+    idx = torch.cuda.current_device() if device is None or device.index is None else device.index
+    n = _CUS.get(idx)
+    if n is None:
+        n = _CUS[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
+    return n
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_NONE, resid=None, out=None,
@@ -221,14 +231,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_NONE, resid
     M, K = a.shape
     N, K2 = w.shape
     _req(K == K2, f"K mismatch {K} vs {K2}")
-    _req(K % 64 == 0, f"K={K} must be a multiple of 64")
-    _req(N % 8 == 0, f"N={N} must be a multiple of 8")
+    p = gemm_plan.plan(M, N, K, epi, cus=_cus(a.device), tile=tile, splits=splits, rms=rms is not None)
     _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.stride(0) >= K, "a must be row-major, 16-B aligned rows")
     _req(w.is_contiguous(), "w must be contiguous")
     _req(a.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0, "operands must be 16-B aligned")
     nout = N // 2 if epi == EPI_SWIGLU else N
-    if epi == EPI_SWIGLU:
-        _req(N % 32 == 0, "SwiGLU needs N % 32 == 0")
     if out is None:
         out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
     _bf16_cuda(out, "out")
@@ -244,25 +251,16 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, epi: int = EPI_NONE, resid
         ldr = resid.stride(0)
     if M == 0:
         return out
-    if (tile == 12 or (tile == 0 and splits <= 0)) and rms is None and dk_fusable(M, N, K, epi):
+    if p.family in ("dk", "dk_splitk"):
         return gemm_dk(a, w, epi=epi, bias=bias, resid=resid, out=out)
-    if tile == 0 and splits <= 0 and gemv_fusable(M, N, K, epi):
-        tile, splits = 6, 1  # batch-1 decode: weight-streaming GEMV, one launch, no split-K workspace
     gamma, eps = (None, 0.0) if rms is None else rms  # rms = (gain or None for unit gain, eps > 0)
     if rms is not None:
-        _req(tile == 6, "fused RMSNorm needs the M == 1 GEMV path")
         _req(eps > 0, "fused RMSNorm needs eps > 0")
         if gamma is not None:
             _bf16_cuda(gamma, "gamma"); _req(gamma.numel() == K, "gamma must be [K]")
-    if splits <= 0:
-        if tile == 0 and M < 640:
-            tile = _decode_tile(M, N)
-        splits = _auto_splits(M, N, K) if tile in (0, 2, 3) or (tile == 9 and M <= 128) else 1
-    ws = None
-    if splits > 1:
-        ws = _workspace(splits * M * N * 4, a.device)
+    ws = _workspace(p.ws_bytes, a.device) if p.ws_bytes else None
     rc = lib().da_gemm_bf16(_ptr(a), a.stride(0), _ptr(w), _ptr(out), out.stride(0), _ptr(bias), _ptr(resid), ldr,
-                            M, N, K, epi, tile, splits, _ptr(ws), _ptr(gamma), float(eps), _stream())
+                            M, N, K, epi, p.tile, p.splits, _ptr(ws), _ptr(gamma), float(eps), _stream())
     _check(rc, "gemm")
     return out
 
@@ -276,57 +274,8 @@ def gemm_route(M: int, N: int, K: int, epi: int = EPI_NONE):
     the GEMV / gemm_dk / weight-streaming family, chosen by more than the tile number."""
     if M <= 128:
         return None
-    if M < 640:
-        tile = _decode_tile(M, N)
-        splits = _auto_splits(M, N, K)
-    else:
-        tile, splits = 0, 1
-    if tile == 0:
-        tile = int(lib().da_gemm_route(M, N, K, splits))
-    return {"tile": tile, "splits": splits}
-
-
-# Decode GEMMs with 2..64 rows: gemm_dk (csrc/gemm_dk.hip: K split across the 4 waves of a
-# workgroup and summed through LDS, no split-K partials, no reduce launch). False: the 64x128 /
-# 32x128 tiles + split-K + reduce (bench/ab_arms.py DA_DECODE_DK=0).
-DECODE_DK = True
-# 33..64 rows keep the gemm_dk layer structure (norms deferred into the consumer) on the split-K
-# tiles: the narrow dk tiles re-read the activation block once per 16-64 weight rows there
-# (bench/midm_chain.py, profiles/r3/dk/), so gemm_dk() routes those rows to da_gemm_dk_splitk
-# (reduce + residual + row sums of squares; the consumer's reduce applies the row scale)
-DK_MAX_M = 64
-DK_SPLITK_ABOVE = 32
-
-
-def dk_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
-    """True when gemm() runs a decode-sized product on gemm_dk (no split-K)."""
-    return (DECODE_DK and 2 <= M <= DK_MAX_M and K % 256 == 0 and N % 16 == 0
-            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
-
-
-def _dk_splitk(M: int, N: int) -> bool:
-    return DK_SPLITK_ABOVE < M <= 64 and N % 512 == 0
-
-
-def _dk_splits(N: int, K: int) -> int:
-    """Split-K of the 33..64-row route (64x128 tiles): the largest of 2, 3, 4, 6, 8, 12, 16 that keeps
-    the grid within one round of 256 workgroups and >= 4 K-steps of 64 per split; at least 2 (the
-    reduce carries the epilogue). 3 is the point of this list: the Phi-3 QKV projection (72 tiles)
-    18.7 us at 3 splits vs 21.8 at 2 and 25.7 at 4 (bench/splitk_m64.py, profiles/r3/splitk_m64.txt)."""
-    tiles, ks = (N + 127) // 128, K // 64
-    best = 2
-    for s in (2, 3, 4, 6, 8, 12, 16):
-        if ks % s == 0 and ks // s >= 4 and tiles * s <= 256:
-            best = s
-    return best if ks % best == 0 else 2
-
-
-def dk_parts(N: int, M: int = 0) -> int:
-    """Row-norm partial sums an EPI_RESID gemm_dk of width N and M rows writes (the consumer's part
-    count): one per dk output tile, or one per 512 columns on the 33..64-row split-K route."""
-    if _dk_splitk(M, N):
-        return N // 512
-    return int(lib().da_gemm_dk_parts(N))
+    p = gemm_plan.plan(M, N, K, epi, cus=_cus())
+    return {"tile": p.tile, "splits": p.splits}
 
 
 def gemm_dk(a, w, epi: int = EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
@@ -356,12 +305,12 @@ def gemm_dk(a, w, epi: int = EPI_NONE, bias=None, resid=None, out=None, norm_in=
     if ssq_out is not None:
         _req(epi == EPI_RESID and ssq_out.dtype == torch.float32 and ssq_out.is_contiguous()
              and ssq_out.numel() >= dk_parts(N, M) * 64, "bad ssq_out")
-    if _dk_splitk(M, N) or (DK_SPLITK_ABOVE < M <= 64 and ssq_out is None):
-        splits = _dk_splits(N, K)
-        ws = _workspace(splits * M * N * 4, a.device)
+    p = gemm_plan.plan_dk(M, N, K, ssq_out is not None)
+    if p.family == "dk_splitk":
+        ws = _workspace(p.ws_bytes, a.device)
         _check(lib().da_gemm_dk_splitk(_ptr(a), a.stride(0), _ptr(w), _ptr(out), out.stride(0), _ptr(bias), _ptr(resid),
                                        ldr, M, N, K, epi, _ptr(ssq), parts, K, float(eps), _ptr(ssq_out), _ptr(ws),
-                                       splits, _stream()), "gemm_dk_splitk")
+                                       p.splits, _stream()), "gemm_dk_splitk")
         return out
     _check(lib().da_gemm_dk(_ptr(a), a.stride(0), _ptr(w), _ptr(out), out.stride(0), _ptr(bias), _ptr(resid), ldr,
                             M, N, K, epi, _ptr(ssq), parts, K, float(eps), _ptr(ssq_out), _stream()), "gemm_dk")
@@ -440,12 +389,6 @@ def quant_weight_fp8_pow2(w: torch.Tensor):
     s = torch.where(amax / (s / 2) <= 448.0, s / 2, s)
     s = torch.where(amax > 0, s, torch.ones_like(s))
     return (wf / s[:, None]).clamp(-448, 448).to(FP8).contiguous(), s.contiguous()
-
-
-def gemv_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
-    """True when gemm_w8() accepts the product: the batch-1 GEMV on fp8 weights (csrc/gemv_w8.hip)."""
-    return (M == 1 and K % 1024 == 0 and N % 4 == 0 and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU)
-            and (epi != EPI_SWIGLU or N % 32 == 0))
 
 
 def gemm_w8(a: torch.Tensor, wq: torch.Tensor, sw: torch.Tensor, bias=None, epi: int = EPI_NONE, resid=None,
@@ -531,57 +474,12 @@ def gemm_resid_norm(a, w, resid, gamma, eps: float, out=None, h_out=None, bias=N
         h_out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     if M == 0:
         return h_out
-    tile = tile or (9 if M > 64 else _decode_tile(M))  # the fused reduce + norm: 128x64 tile above 64 rows
-    if splits <= 0:
-        splits = _auto_splits(M, N, K)
-    ws = _workspace(splits * M * N * 4, a.device)
+    p = gemm_plan.plan_resid_norm(M, N, K, tile, splits)
+    ws = _workspace(p.ws_bytes, a.device)
     _check(lib().da_gemm_resid_rmsnorm(_ptr(a), a.stride(0), _ptr(w), _ptr(out), out.stride(0), _ptr(bias),
-                                       _ptr(resid), resid.stride(0), M, N, K, tile, splits, _ptr(ws), _ptr(gamma),
+                                       _ptr(resid), resid.stride(0), M, N, K, p.tile, p.splits, _ptr(ws), _ptr(gamma),
                                        float(eps), _ptr(h_out), h_out.stride(0), _stream()), "gemm_resid_norm")
     return h_out
-
-
-def _decode_tile(M: int, N: int = 0) -> int:
-    """Decode-sized M: 32x128 tiles up to 32 rows, 64x128 to 64; 65..128 rows (a batch-128 decode
-    step): N >= 8192 (QKV, gate/up, LM head: >= 128 weight tiles) the 64x128 tile over the two row
-    blocks without split-K, else one 128x64 weight-streaming tile per 64 weight rows with split-K
-    (profiles/r5/midm/decode_gemm_sweep_m128.txt, weights cold: QKV 28.0 vs 33.5 us, gate/up 30.5 vs
-    47.4 us at 128 rows vs the 128x64 tile at split 4; O / down best on the 128x64 tile at split 4);
-    129..639 rows the 64x128 tile over ceil(M/64) row blocks."""
-    if M <= 32:
-        return 3
-    if 64 < M <= 128:
-        return 2 if N >= 8192 else 9
-    return 2
-
-
-def _auto_splits(M: int, N: int, K: int) -> int:
-    """Split-K for decode-sized M: the largest power of two keeping <= 256 workgroups (one per CU)
-    and >= 4 K-steps per split. With 4 k-tiles in flight per workgroup (gemm.hip PF) a tile needs
-    fewer splits to cover HBM latency, and fewer splits = fewer partial bytes to reduce. From a
-    graph-replayed sweep with weights streamed cold from HBM, as in a real decode step
-    (profiles/decode_gemm_prefetch_sweep_r1.jsonl: matches the best split on 17 of 20 Phi-3 /
-    Llama-3-8B shapes at M = 16 / 64, within 0.7 us on the rest)."""
-    if M >= 640:
-        return 1
-    ksteps = K // 64
-    if 64 < M <= 128:  # (see _decode_tile) wide N: no split; else 4 splits, fewer if K is short
-        if N >= 8192:
-            return 1
-        s = 4
-        while s > 1 and (ksteps % s or ksteps // s < 4):
-            s //= 2
-        return s
-    tiles = math.ceil(M / (32 if _decode_tile(M) == 3 else 64)) * math.ceil(N / 128)
-    # 65..639 rows run the 64x128 tile over ceil(M/64) row blocks (the row blocks of one weight tile
-    # share it through L2): up to 4 workgroups per CU below 256 rows, 2.5 from 256 (32-layer Phi-3
-    # chain, bench/midm_chain.py, profiles/r2/midm_chain.txt: split 4 best at M = 65 / 128, 2 at 192 /
-    # 256, 1 from 384)
-    cap = 256 if M <= 64 else (1024 if M < 256 else 640)
-    s = 1
-    while tiles * s * 2 <= cap and ksteps % (s * 2) == 0 and ksteps // (s * 2) >= 4:
-        s *= 2
-    return s
 
 
 # ------------------------------------------------------------------------------ norms etc.
@@ -1118,7 +1016,7 @@ def gemm_f16(a, w, bias=None, epi: int = EPI_NONE, resid=None, out=None) -> torc
         out = torch.empty((M, N), dtype=torch.float16, device=a.device)
     _req(out.dtype == torch.float16 and out.shape == (M, N) and out.stride(1) == 1 and out.stride(0) % 8 == 0, "out")
     _check(lib().da_gemm_f16(_ptr(a), a.stride(0), _ptr(w), _ptr(out), out.stride(0), _ptr(bias), _ptr(resid), ldr,
-                             M, N, K, epi, _stream()), "gemm_f16")
+                             M, N, K, epi, gemm_plan.prefill_bm(M, N, _cus(a.device)), _stream()), "gemm_f16")
     return out
 
 

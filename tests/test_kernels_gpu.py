@@ -165,7 +165,7 @@ def test_gemm_mid_m_in_tree(M):
     torch.manual_seed(M)
     N, F, Kd = 3072, 1024, 3072
     a, w = _rand(M, Kd), _rand(N, Kd, scale=Kd ** -0.5)
-    assert K._auto_splits(M, N, Kd) > 1
+    assert K.gemm_plan.auto_splits(M, N, Kd) > 1
     ref = a.float() @ w.float().t()
     _close(K.gemm(a, w), ref, atol=0.03)
     resid = _rand(M, N)
