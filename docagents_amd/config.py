@@ -54,6 +54,9 @@ class Config:
     # decoder weight storage: bf16, or fp8 = the decoder quantised per output row to OCP e4m3 with an
     # e4m3 copy of every matmul weight that the batch-1 decode GEMVs stream (TP_SIZE=1 only)
     llm_weight_dtype: str = field(default="bf16", metadata={"env": "LLM_WEIGHT_DTYPE"})
+    # decoder KV-cache storage: bf16, or fp8 = every cached K / V row as e4m3 codes + one power-of-two
+    # fp32 scale (D + 4 bytes per row instead of 2 D): a throughput / capacity option (TP_SIZE=1 only)
+    kv_cache_dtype: str = field(default="bf16", metadata={"env": "KV_CACHE_DTYPE"})
     tp_size: int = field(default=1, metadata={"env": "TP_SIZE"})
     index_shards: int = field(default=1, metadata={"env": "INDEX_SHARDS"})
     index_kind: str = field(default="flat", metadata={"env": "INDEX_KIND"})
@@ -141,6 +144,7 @@ class Config:
     # Anything else is refused at startup, never run as something else.
     ENGINE_DTYPES = ("bf16", "fp16", "fp8")
     LLM_WEIGHT_DTYPES = ("bf16", "fp8")
+    KV_CACHE_DTYPES = ("bf16", "fp8")
 
     def validate_engine(self) -> "Config":
         """Startup check of the engine keys whose wrong value would otherwise silently run a
@@ -157,6 +161,12 @@ class Config:
         if self.llm_weight_dtype == "fp8" and self.tp_size > 1:
             # quantising per TP shard is a different model from quantising the whole
             raise ValueError("LLM_WEIGHT_DTYPE=fp8 needs TP_SIZE=1")
+        if self.kv_cache_dtype not in self.KV_CACHE_DTYPES:
+            raise ValueError(f"KV_CACHE_DTYPE={self.kv_cache_dtype!r} is not supported "
+                             f"(choose one of {', '.join(self.KV_CACHE_DTYPES)})")
+        if self.kv_cache_dtype == "fp8" and self.tp_size > 1:
+            # the per-head quantisation is shard-independent, but no TP test covers the combination
+            raise ValueError("KV_CACHE_DTYPE=fp8 needs TP_SIZE=1")
         if self.search_transport not in ("plane", "rccl"):
             raise ValueError(f"SEARCH_TRANSPORT={self.search_transport!r} is not supported (plane | rccl)")
         if self.search_transport == "rccl" and self.tp_size > 1:

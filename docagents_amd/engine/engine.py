@@ -43,7 +43,7 @@ class Engine:
                  ivf_lists: int = 100, ivf_probes: int = 1, load_llm: bool = True, load_encoder: bool = True,
                  use_graphs: bool = True, embed_max_tokens: int = 65536, enc_dtype: str = "bf16",
                  share_prefix: bool = True, overlap_waves: bool = False, kv_cache_gb: float = 0.0,
-                 llm_weight_dtype: str = "bf16"):
+                 llm_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16"):
         self.device = torch.device(device)
         self.lock = threading.RLock()      # the decoder / generator (one GPU thread drives it)
         self.enc_lock = threading.RLock()  # the encoder: the fast embed lane and the batcher share it
@@ -67,7 +67,10 @@ class Engine:
         if load_llm:
             # "fp8": an e4m3 copy of the matmul weights (+ 1 byte per weight of HBM) that the batch-1
             # decode GEMVs stream; auto_batch below sizes the KV cache from what is free after it
-            self.decoder = LlamaDecoder(self.dec_cfg, self.device, seed=seed, tp=tp, weight_dtype=llm_weight_dtype)
+            # kv_cache_dtype "fp8": the KV cache as e4m3 codes + a scale per row (D + 4 bytes instead of
+            # 2 D); auto_batch sizes the cache with that row size
+            self.decoder = LlamaDecoder(self.dec_cfg, self.device, seed=seed, tp=tp, weight_dtype=llm_weight_dtype,
+                                        kv_dtype=kv_cache_dtype)
             if max_batch <= 0:
                 max_batch = self.auto_batch(max_seq, overlap_waves, kv_gb=kv_cache_gb)
             # + 1 dummy slot (padded graph rows) + 2 prompt-head slots (ContinuousScheduler heads)
@@ -90,11 +93,12 @@ class Engine:
         """``max_batch=0``: the largest power-of-two decode batch (<= AUTO_BATCH_MAX) whose KV cache
         (batch + 4 slots x max_seq, this rank's kv heads) fits ``kv_gb`` GB, or the device's free
         HBM after the weights less AUTO_RESERVE_BYTES. Phi-3-mini on an MI355X: 128 (213 GB of
-        KV); Llama-3-70B on one GPU: 16. CPU: 64."""
+        KV; 111 GB with the fp8 cache); Llama-3-70B on one GPU: 16. CPU: 64."""
         from ..models.llama import KVCache
         if self.device.type != "cuda" and kv_gb <= 0:
             return 64
-        per = KVCache.bytes_for(self.dec_cfg, 1, min(max_seq, self.dec_cfg.max_pos), self.decoder.tp.size)
+        per = KVCache.bytes_for(self.dec_cfg, 1, min(max_seq, self.dec_cfg.max_pos), self.decoder.tp.size,
+                                dtype=self.decoder.kv_dtype)
         if kv_gb > 0:
             budget = int(kv_gb * 1e9)
         else:

@@ -6,7 +6,9 @@ N6-N8). Per layer (hidden state x is the residual stream, updated in place):
     h   = RMSNorm(x)                                   rmsnorm kernel
     qkv = h @ Wqkv^T                                   MFMA GEMM   (column-parallel: local heads)
     RoPE(q, k) + write k, v to the KV cache            prefill: the GEMM's epilogue; decode: the
-                                                       attention kernel (MHA) / rope_cache (GQA)
+                                                       attention kernel (MHA) / rope_cache (GQA);
+                                                       kv_dtype="fp8": rope_cache_kv8 (e4m3 codes
+                                                       + a power-of-two scale per cached row)
     a   = attention(q, K, V)                           varlen flash prefill / split-KV decode
     x   = x + a @ Wo^T                                 GEMM + fused residual epilogue (row-parallel
                                                        -> RCCL all-reduce over xGMI when TP > 1)
@@ -194,14 +196,29 @@ def random_weights(cfg: DecoderConfig, device, seed: int = 0, tp_rank: int = 0, 
     return w
 
 
-class KVCache:
-    """Contiguous per-slot KV cache: k/v [layers][slots, Hkv_local, max_seq, D] (one allocation)."""
+KV_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 codes + one power-of-two fp32 scale per cached row
 
-    def __init__(self, cfg: DecoderConfig, slots: int, max_seq: int, tp_size: int, device):
-        self.slots, self.max_seq = slots, max_seq
+
+class KVCache:
+    """Contiguous per-slot KV cache: k/v [layers][slots, Hkv_local, max_seq, D] (one allocation).
+
+    dtype="fp8": every cached row (one token, one kv head, D values) is stored as D e4m3 codes and
+    one fp32 power-of-two scale (quant_weight_fp8_pow2's rule; code * scale is exact in bf16):
+    ``codes`` [layers, 2, slots, Hkv, max_seq, D] one byte each, ``scales`` [layers, 2, slots, Hkv,
+    max_seq] — D + 4 bytes per row instead of 2 D. ``buf`` is None then."""
+
+    def __init__(self, cfg: DecoderConfig, slots: int, max_seq: int, tp_size: int, device, dtype: str = "bf16"):
+        if dtype not in KV_DTYPES:
+            raise ValueError(f"KV cache dtype={dtype!r} is not supported ({' | '.join(KV_DTYPES)})")
+        self.slots, self.max_seq, self.dtype = slots, max_seq, dtype
         self.hkv = cfg.kv_heads // tp_size
-        self.buf = torch.zeros((cfg.layers, 2, slots, self.hkv, max_seq, cfg.head_dim), dtype=torch.bfloat16,
-                               device=device)
+        shape = (cfg.layers, 2, slots, self.hkv, max_seq, cfg.head_dim)
+        self.buf = self.codes = self.scales = None
+        if dtype == "fp8":
+            self.codes = torch.zeros(shape, dtype=torch.uint8, device=device).view(torch.float8_e4m3fn)
+            self.scales = torch.ones(shape[:-1], dtype=torch.float32, device=device)  # an all-zero row: scale 1
+        else:
+            self.buf = torch.zeros(shape, dtype=torch.bfloat16, device=device)
         self.free = list(range(slots - 1, -1, -1))
 
     def k(self, layer):
@@ -209,6 +226,10 @@ class KVCache:
 
     def v(self, layer):
         return self.buf[layer, 1]
+
+    def kv8(self, layer):
+        """(k_codes, v_codes, k_scale, v_scale) of one layer (dtype="fp8")."""
+        return self.codes[layer, 0], self.codes[layer, 1], self.scales[layer, 0], self.scales[layer, 1]
 
     def acquire(self, n: int) -> list[int]:
         if n > len(self.free):
@@ -219,8 +240,11 @@ class KVCache:
         self.free.extend(ids)
 
     @staticmethod
-    def bytes_for(cfg: DecoderConfig, slots: int, max_seq: int, tp_size: int = 1) -> int:
-        return cfg.layers * 2 * slots * (cfg.kv_heads // tp_size) * max_seq * cfg.head_dim * 2
+    def bytes_for(cfg: DecoderConfig, slots: int, max_seq: int, tp_size: int = 1, dtype: str = "bf16") -> int:
+        if dtype not in KV_DTYPES:
+            raise ValueError(f"KV cache dtype={dtype!r} is not supported ({' | '.join(KV_DTYPES)})")
+        row = cfg.head_dim + 4 if dtype == "fp8" else cfg.head_dim * 2  # fp8: D codes + one fp32 scale
+        return cfg.layers * 2 * slots * (cfg.kv_heads // tp_size) * max_seq * row
 
 
 WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMV chain
@@ -231,13 +255,19 @@ class LlamaDecoder:
     layer_hook = None   # prefill: called with the layer index before each layer (stream steering)
 
     def __init__(self, cfg: DecoderConfig, device="cuda", seed: int = 0, tp: TPContext | None = None,
-                 weights: dict | None = None, weight_dtype: str = "bf16"):
+                 weights: dict | None = None, weight_dtype: str = "bf16", kv_dtype: str = "bf16"):
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype={weight_dtype!r} is not supported ({' | '.join(WEIGHT_DTYPES)})")
         if weight_dtype == "fp8" and tp is not None and tp.size > 1:
             # quantising per shard is a different model from quantising the whole
             raise ValueError("weight_dtype='fp8' needs TP size 1")
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype={kv_dtype!r} is not supported ({' | '.join(KV_DTYPES)})")
+        if kv_dtype == "fp8" and tp is not None and tp.size > 1:
+            # per-head quantisation is shard-independent, but no TP test covers the combination yet
+            raise ValueError("kv_dtype='fp8' needs TP size 1")
         self.weight_dtype = weight_dtype
+        self.kv_dtype = kv_dtype  # "fp8": e4m3 KV cache (KVCache dtype); prefill / decode take the kv8 ops
         self.cfg = cfg
         self.device = torch.device(device)
         self.ops = get_ops(self.device)
@@ -299,7 +329,7 @@ class LlamaDecoder:
 
     def alloc_cache(self, slots: int, max_seq: int) -> KVCache:
         max_seq = min(max_seq, self.cfg.max_pos)
-        self.cache = KVCache(self.cfg, slots, max_seq, self.tp.size, self.device)
+        self.cache = KVCache(self.cfg, slots, max_seq, self.tp.size, self.device, dtype=self.kv_dtype)
         return self.cache
 
     # ------------------------------------------------------------- shared layer body
@@ -386,7 +416,9 @@ class LlamaDecoder:
         D, hl, kl = c.head_dim, self.hl, self.kl
         x = o.embed(ids, self.w["embed"])
         hook = self.layer_hook
-        kv_from_cache = bool(getattr(o, "flash_kv_cache_ok", lambda *_: False)(D, True))
+        kv8 = self.kv_dtype == "fp8"
+        # fp8 cache: the attention reads the sequences' own k / v from the (unquantised) qkv rows
+        kv_from_cache = not kv8 and bool(getattr(o, "flash_kv_cache_ok", lambda *_: False)(D, True))
         M, last = x.shape[0], len(self.w["layers"]) - 1
         # the last layer's hidden rows are read at last_idx only (its K / V rows by decode, from the
         # cache): past its QKV projection it runs on those rows alone, with the full pass's bits
@@ -397,9 +429,17 @@ class LlamaDecoder:
             h = o.rmsnorm(x, L["ln_attn"], c.eps)
             # QKV projection + RoPE + KV-cache write in one kernel (gemm8p EPI_ROPE epilogue); where the
             # attention reads its keys from the cache (Phi-3's D = 96), k / v go to the cache only
-            qkv = o.gemm_rope(h, L["wqkv"], pos, self.cos_sin, hl, kl, D, slot_tok, cache.k(li), cache.v(li),
-                              kv_out=not kv_from_cache)
-            pre = None if prefix is None else (cache.k(li)[prefix[0]], cache.v(li)[prefix[0]], prefix[1])
+            if kv8:
+                # the unfused path gemm_rope takes for short prefills, with the quantising cache write;
+                # the shared prefix is dequantised (exactly) to bf16 for the flash kernel, per layer
+                kq, vq, ks, vs = cache.kv8(li)
+                qkv = o.rope_cache_kv8(o.gemm(h, L["wqkv"]), pos, self.cos_sin, hl, kl, D, slot_tok, kq, vq, ks, vs)
+                pre = None if prefix is None else (o.kv8_dequant(kq, ks, prefix[0], prefix[1]),
+                                                   o.kv8_dequant(vq, vs, prefix[0], prefix[1]), prefix[1])
+            else:
+                qkv = o.gemm_rope(h, L["wqkv"], pos, self.cos_sin, hl, kl, D, slot_tok, cache.k(li), cache.v(li),
+                                  kv_out=not kv_from_cache)
+                pre = None if prefix is None else (cache.k(li)[prefix[0]], cache.v(li)[prefix[0]], prefix[1])
             cut = tail is not None and li == last
             if kv_from_cache:
                 a = o.flash_attn_varlen(qkv[:, :hl * D], None, None, cu, max_seqlen, hl, kl, D, causal=True,
@@ -445,9 +485,15 @@ class LlamaDecoder:
     def _decode_attn(self, qkv, li: int, st: "DecodeState"):
         """RoPE + new-token cache write + decode attention. MHA (Phi-3): one launch — the attention
         kernel rotates q / the new k itself and writes the new k / v to the cache; GQA: rope_cache,
-        then the MFMA decode kernel."""
+        then the MFMA decode kernel. fp8 KV cache: rope_cache_kv8, then decode_attn_kv8 (one launch
+        more per layer than the fused MHA form)."""
         c, o, cache = self.cfg, self.ops, self.cache
         D, hl, kl = c.head_dim, self.hl, self.kl
+        if self.kv_dtype == "fp8":  # every batch size, MHA and GQA: quantising cache write, then attention
+            kq, vq, ks, vs = cache.kv8(li)
+            o.rope_cache_kv8(qkv, st.pos, self.cos_sin, hl, kl, D, st.slot, kq, vq, ks, vs)
+            return o.decode_attn_kv8(qkv, kq, vq, ks, vs, st.lens, st.slot, hl, kl, D, max_len=cache.max_seq,
+                                     pre=st.pre, out=st.attn)
         if hl == kl and _FUSED_ROPE_DECODE:
             return o.decode_attn(qkv, cache.k(li), cache.v(li), st.lens, st.slot, hl, kl, D, max_len=cache.max_seq,
                                  pre=st.pre, rope=(self.cos_sin, st.pos), out=st.attn)

@@ -72,6 +72,10 @@ _SIGS = {
     "da_decode_attn": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                        c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                        c_int, c_void_p],
+    "da_rope_cache_kv8": [c_void_p] * 8 + [c_int] * 6 + [c_void_p],
+    "da_kv8_dequant": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "da_decode_attn_kv8": [c_void_p, c_int] + [c_void_p] * 7 + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_int,
+                                                                                c_void_p, c_void_p],
     "da_topk_dense": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_int,
                       c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "da_topk_dense_stream": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_int,
@@ -774,6 +778,89 @@ def decode_attn(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len: int, chunk:
     _check(lib().da_decode_attn(_ptr(q), q.stride(0), _ptr(k_cache), _ptr(v_cache), _ptr(lens), _ptr(slot), _ptr(pre), B, H,
                                 Hkv, D, k_cache.shape[2], chunk, nsplit, float(scale), _ptr(ws), _ptr(out), out.stride(0),
                                 _ptr(cnt), _ptr(cs), _ptr(ps), xc, _stream()), "decode_attn")
+    return out
+
+
+# ----------------------------------------------------------------------------------- fp8 KV cache
+def _kv8_cache_checks(k_codes, v_codes, k_scale, v_scale, Hkv, D):
+    for c, s, n in ((k_codes, k_scale, "k"), (v_codes, v_scale, "v")):
+        _req(c.is_cuda and c.dtype in (FP8, torch.uint8) and c.is_contiguous(), f"{n}_codes must be contiguous e4m3 on GPU")
+        _req(c.dim() == 4 and c.shape[1] == Hkv and c.shape[3] == D, f"{n}_codes [slots, Hkv, max_seq, D]")
+        _req(s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.shape == c.shape[:3],
+             f"{n}_scale must be contiguous fp32 [slots, Hkv, max_seq]")
+        _req(c.data_ptr() % 16 == 0 and s.data_ptr() % 4 == 0, f"{n} cache alignment")
+    _req(k_codes.shape == v_codes.shape, "k / v caches differ in shape")
+
+
+def rope_cache_kv8(qkv, pos, cos_sin, H, Hkv, D, slot, k_codes, v_codes, k_scale, v_scale, rotate_q=True):
+    """In-place RoPE on the q and k heads of qkv [T, (H+2Hkv)*D] (the roundings of rope_cache), then
+    the rotated k row and the v row of every (token, kv head) quantised to e4m3 with one power-of-two
+    scale per row (quant_weight_fp8_pow2's rule) and written to the fp8 cache at [slot[t], :, pos[t]]
+    (codes [slots, Hkv, max_seq, D], scales fp32 [slots, Hkv, max_seq]). pos[t] < max_seq and
+    0 <= slot[t] < slots are the caller's contract, as for rope_cache."""
+    _bf16_cuda(qkv, "qkv"); _i32(pos, "pos"); _i32(slot, "slot")
+    T = qkv.shape[0]
+    _req(D in (64, 96, 128), "head dim")
+    _req(qkv.is_contiguous() and qkv.shape[1] == (H + 2 * Hkv) * D and qkv.data_ptr() % 16 == 0, "qkv shape")
+    _req(pos.numel() >= T and slot.numel() >= T, "pos / slot length")
+    _req(cos_sin.is_cuda and cos_sin.dtype == torch.float32 and cos_sin.is_contiguous() and cos_sin.dim() == 3
+         and cos_sin.shape[-1] == 2 and cos_sin.shape[1] == D // 2, "cos_sin must be fp32 [max_pos, D/2, 2]")
+    _kv8_cache_checks(k_codes, v_codes, k_scale, v_scale, Hkv, D)
+    _check(lib().da_rope_cache_kv8(_ptr(qkv), _ptr(pos), _ptr(slot), _ptr(cos_sin), _ptr(k_codes), _ptr(v_codes),
+                                   _ptr(k_scale), _ptr(v_scale), T, H, Hkv, D, k_codes.shape[2],
+                                   1 if rotate_q else 0, _stream()), "rope_cache_kv8")
+    return qkv
+
+
+def decode_attn_kv8(q, k_codes, v_codes, k_scale, v_scale, lens, slot, H, Hkv, D, max_len: int, chunk: int = 0,
+                    scale=None, out=None, pre=None):
+    """decode_attn (without rope=) over the fp8 cache: q [B, >= H*D] bf16 (any row stride), lens / slot
+    int32 [B], max_len fixes the split count (graph-capturable), pre int32 [B, 2] = (P, prefix slot)
+    with P % 64 == 0, out bf16 with any row stride. Splits merge in the kernel through the uncached
+    workspace and ticket (or a combine launch with _FUSED_COMBINE off); never the same-XCD exchange."""
+    _bf16_cuda(q, "q"); _i32(lens, "lens"); _i32(slot, "slot")
+    _req(D in (64, 96, 128), "head dim")
+    _req(H % Hkv == 0 and (H // Hkv) in (1, 2, 4, 8), "GQA group must be 1/2/4/8")
+    _req(q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= H * D, "q [B, >= H*D]")
+    B = q.shape[0]
+    _req(lens.numel() >= B and slot.numel() >= B, "lens / slot length")
+    _kv8_cache_checks(k_codes, v_codes, k_scale, v_scale, Hkv, D)
+    _req(0 < max_len <= k_codes.shape[2], "max_len > cache capacity")
+    if pre is not None:
+        _i32(pre, "pre"); _req(pre.shape == (B, 2) and pre.is_contiguous(), "pre must be int32 [B, 2]")
+    chunk, nsplit = _decode_split(B, Hkv, max_len, chunk)
+    _req(chunk % 64 == 0, "chunk must be a multiple of 64")
+    if out is None:
+        out = torch.empty((B, H * D), dtype=torch.bfloat16, device=q.device)
+    _bf16_cuda(out, "out")
+    _req(out.dim() == 2 and out.shape[0] == B and out.shape[1] >= H * D and out.stride(1) == 1, "out [B, >= H*D]")
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    nws = B * H * nsplit * (D + 2) * 4
+    ws = _workspace(nws, q.device)
+    cnt = None
+    if _FUSED_COMBINE and nsplit > 1:
+        cnt = _uncached("decode_cnt", B * Hkv * 4, q.device)
+        ws = _uncached("decode_ws", nws, q.device)
+    _check(lib().da_decode_attn_kv8(_ptr(q), q.stride(0), _ptr(k_codes), _ptr(v_codes), _ptr(k_scale), _ptr(v_scale),
+                                    _ptr(lens), _ptr(slot), _ptr(pre), B, H, Hkv, D, k_codes.shape[2], chunk, nsplit,
+                                    float(scale), _ptr(ws), _ptr(out), out.stride(0), _ptr(cnt), _stream()),
+           "decode_attn_kv8")
+    return out
+
+
+def kv8_dequant(codes, scale, slot: int, P: int):
+    """bf16 [Hkv, P, D]: the first P keys of cache slot ``slot`` (host int) dequantised, exactly — the
+    shared prefix the flash prefill reads in bf16."""
+    slot, P = int(slot), int(P)
+    _req(codes.is_cuda and codes.dtype in (FP8, torch.uint8) and codes.is_contiguous() and codes.dim() == 4
+         and codes.shape[3] % 16 == 0 and codes.data_ptr() % 16 == 0, "codes [slots, Hkv, max_seq, D]")
+    _req(scale.is_cuda and scale.dtype == torch.float32 and scale.is_contiguous() and scale.shape == codes.shape[:3],
+         "scale fp32 [slots, Hkv, max_seq]")
+    S, Hkv, max_seq, D = codes.shape
+    _req(0 <= slot < S and 0 <= P <= max_seq, "slot / P out of range")
+    out = torch.empty((Hkv, P, D), dtype=torch.bfloat16, device=codes.device)
+    _check(lib().da_kv8_dequant(_ptr(codes), _ptr(scale), slot, S, Hkv, P, D, max_seq, _ptr(out), _stream()),
+           "kv8_dequant")
     return out
 
 

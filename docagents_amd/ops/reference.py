@@ -494,6 +494,53 @@ def quant_weight_fp8_pow2(w):
     return (wf / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), s.contiguous()
 
 
+# ----------------------------------------------------------------------------------- fp8 KV cache
+# codes [slots, Hkv, max_seq, D] float8_e4m3fn + scales [slots, Hkv, max_seq] fp32: every cached row
+# is quant_weight_fp8_pow2 of the bf16 row (power-of-two scale: code * scale is exact in bf16).
+def kv8_dequant_all(codes, scale):
+    """The whole cache tensor (any leading dims) dequantised to bf16 (exact)."""
+    return (codes.float() * scale[..., None].float()).to(torch.bfloat16)
+
+
+def rope_cache_kv8(qkv, pos, cos_sin, H, Hkv, D, slot, k_codes, v_codes, k_scale, v_scale, rotate_q=True):
+    """rope_cache on qkv (in place, the same roundings), then the rotated k row and the v row of every
+    (token, kv head) quantised into the fp8 cache at [slot[t], :, pos[t]]."""
+    T = qkv.shape[0]
+    rope_cache(qkv, pos[:T], cos_sin, H, Hkv, D, rotate_q=rotate_q)
+    x = qkv.view(T, H + 2 * Hkv, D)
+    sl, ps = slot[:T].long(), pos[:T].long()
+    for rows, codes, scale in ((x[:, H:H + Hkv], k_codes, k_scale), (x[:, H + Hkv:], v_codes, v_scale)):
+        q, s = quant_weight_fp8_pow2(rows.reshape(T * Hkv, D))
+        codes.view(torch.uint8)[sl, :, ps] = q.view(torch.uint8).view(T, Hkv, D)  # index_put on bytes
+        scale[sl, :, ps] = s.view(T, Hkv)
+    return qkv
+
+
+def decode_attn_kv8(q, k_codes, v_codes, k_scale, v_scale, lens, slot, H, Hkv, D, max_len=None, chunk=0, scale=None,
+                    out=None, pre=None):
+    """decode_attn over the dequantised cache (dequantisation is exact in bf16, so this IS decode_attn
+    on a bf16 cache that holds those values). Only the slots the call reads are dequantised."""
+    used = set(int(s) for s in slot.tolist())
+    if pre is not None:
+        used |= set(int(p[1]) for p in pre.tolist() if p[0] > 0)
+    idx = torch.tensor(sorted(used), dtype=torch.long, device=k_codes.device)
+    remap = {s: i for i, s in enumerate(idx.tolist())}
+    kc = kv8_dequant_all(k_codes.view(torch.uint8)[idx].view(k_codes.dtype), k_scale[idx])
+    vc = kv8_dequant_all(v_codes.view(torch.uint8)[idx].view(v_codes.dtype), v_scale[idx])
+    slot2 = torch.tensor([remap[int(s)] for s in slot.tolist()], dtype=torch.int32, device=slot.device)
+    pre2 = None
+    if pre is not None:
+        pre2 = torch.tensor([[p[0], remap[int(p[1])] if p[0] > 0 else 0] for p in pre.tolist()], dtype=torch.int32,
+                            device=pre.device).view(-1, 2)
+    return decode_attn(q, kc, vc, lens, slot2, H, Hkv, D, max_len=max_len, scale=scale, out=out, pre=pre2)
+
+
+def kv8_dequant(codes, scale, slot, P):
+    """bf16 [Hkv, P, D]: the first P keys of one slot, dequantised (the flash prefill's shared prefix)."""
+    slot, P = int(slot), int(P)
+    return kv8_dequant_all(codes[slot, :, :P], scale[slot, :, :P]).contiguous()
+
+
 def gemv_w8_fusable(M, N, K, epi=EPI_NONE):
     return M == 1 and K % 1024 == 0
 

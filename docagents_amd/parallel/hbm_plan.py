@@ -51,9 +51,9 @@ def decoder_weight_bytes(cfg: DecoderConfig, tp: int = 1) -> int:
     return 2 * (cfg.vocab * h + cfg.vocab * h // tp + cfg.layers * per_layer + h)
 
 
-def kv_bytes(cfg: DecoderConfig, slots: int, max_seq: int, tp: int = 1) -> int:
+def kv_bytes(cfg: DecoderConfig, slots: int, max_seq: int, tp: int = 1, dtype: str = "bf16") -> int:
     from ..models.llama import KVCache
-    return KVCache.bytes_for(cfg, slots, min(max_seq, cfg.max_pos), tp)
+    return KVCache.bytes_for(cfg, slots, min(max_seq, cfg.max_pos), tp, dtype=dtype)
 
 
 def workspace_bytes(cfg: DecoderConfig, max_batch: int, max_seq: int, tp: int = 1) -> int:
@@ -106,6 +106,7 @@ class BenchArgs:
     max_seq: int = 4096
     tp70b: bool | None = None  # None: bench.py's "auto" (on at N = 8)
     ingest: bool = True        # --ingest-docs > 0: documents are added to the index (it grows)
+    kv_dtype: str = "bf16"     # the engine's KV-cache storage (KV_CACHE_DTYPE); bench.py runs bf16
 
 
 def bench_plan(a: BenchArgs, world: int, release_engine_kv: bool = True) -> dict:
@@ -122,7 +123,7 @@ def bench_plan(a: BenchArgs, world: int, release_engine_kv: bool = True) -> dict
         "decoder_weights": decoder_weight_bytes(dec, tp),
         "index": index_bytes(a.index_rows, enc.hidden),
     }
-    engine_kv = kv_bytes(dec, slots, eng_seq, tp)
+    engine_kv = kv_bytes(dec, slots, eng_seq, tp, a.kv_dtype)
     phases: dict = {}
     setup = dict(resident)
     setup.update({"engine_kv": engine_kv, "index_build": index_build_bytes(a.index_rows, enc.hidden)})
