@@ -60,15 +60,18 @@ def main():
     ap.add_argument("--probes", default="8,32")
     ap.add_argument("--batches", default="1,64,512")
     ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8"), help="flat index row storage (INDEX_DTYPE)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.dtype == "fp8" and a.kind != "flat":
+        ap.error("--dtype fp8 needs --kind flat")
     dev = torch.device("cuda")
     gen, C = make_gen(a.dim, a.chunk, a.rows)
     nch = (a.rows + a.chunk - 1) // a.chunk
-    res = {"kind": a.kind, "rows": a.rows, "dim": a.dim, "k": a.k}
+    res = {"kind": a.kind, "dtype": a.dtype, "rows": a.rows, "dim": a.dim, "k": a.k}
     t0 = time.perf_counter()
     if a.kind == "flat":
-        ix = FlatIndex(a.dim, dev, capacity=a.rows)
+        ix = FlatIndex(a.dim, dev, capacity=a.rows, dtype=a.dtype)
         ndoc = (a.rows + a.rows_per_doc - 1) // a.rows_per_doc
         for c in range(nch):
             x = gen(c)
@@ -83,7 +86,9 @@ def main():
             gen, a.rows, a.chunk, a.rows_per_doc, iters=8, sample=min(a.rows, 64 * a.lists))
     torch.cuda.synchronize()
     res["build_s"] = round(time.perf_counter() - t0, 2)
-    res["hbm_index_gb"] = round(ix.X.numel() * 2 / 1e9, 2)
+    fp8 = a.dtype == "fp8"
+    row_bytes = a.dim + 4 if fp8 else a.dim * 2  # what a scan reads per row
+    res["hbm_index_gb"] = round(ix.slots_t.shape[0] * row_bytes / 1e9, 2)
     res["hbm_allocated_gb"] = round(torch.cuda.memory_allocated() / 1e9, 2)
     print(json.dumps(res), flush=True)
 
@@ -95,11 +100,15 @@ def main():
         q = torch.nn.functional.normalize(C[lab] + 0.35 / a.dim ** 0.5 * torch.randn(B, a.dim, device=dev, generator=gq),
                                           dim=-1).to(torch.bfloat16)
         # exact reference over the whole store
-        es, ei = ix.ops.topk_dense(ix.X[:ix.n].contiguous(), q, a.k, -2.0)
+        def exact():
+            if fp8:
+                return ix.ops.topk_dense8(ix.codes[:ix.n], ix.scale, q, a.k, -2.0)
+            return ix.ops.topk_dense(ix.X[:ix.n].contiguous(), q, a.k, -2.0)
+        es, ei = exact()
         exact_ids = ix.gather_ids(ei).cpu().numpy()
-        t_exact = timeit(lambda: ix.ops.topk_dense(ix.X[:ix.n].contiguous(), q, a.k, -2.0), reps=3)
+        t_exact = timeit(exact, reps=3)
         entry = {"batch": B, "exact_scan_ms": round(t_exact * 1e3, 3),
-                 "exact_scan_tbps": round(ix.n * a.dim * 2 / t_exact / 1e12, 2)}
+                 "exact_scan_tbps": round(ix.n * row_bytes / t_exact / 1e12, 2)}
         filt = [[f"d{(i * 7919) % max(1, a.rows // a.rows_per_doc)}" for i in range(b, b + 8)] for b in range(B)]
         for p in probes:
             if a.kind == "ivfflat":

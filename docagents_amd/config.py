@@ -60,6 +60,9 @@ class Config:
     tp_size: int = field(default=1, metadata={"env": "TP_SIZE"})
     index_shards: int = field(default=1, metadata={"env": "INDEX_SHARDS"})
     index_kind: str = field(default="flat", metadata={"env": "INDEX_KIND"})
+    # flat-index row storage: bf16, or fp8 = every row as e4m3 codes + one power-of-two fp32 scale
+    # (dim + 4 bytes per row instead of 2 dim): a capacity / bandwidth option (INDEX_KIND=flat only)
+    index_dtype: str = field(default="bf16", metadata={"env": "INDEX_DTYPE"})
     ivf_lists: int = field(default=100, metadata={"env": "IVF_LISTS"})
     ivf_probes: int = field(default=1, metadata={"env": "IVF_PROBES"})
     min_similarity: float = field(default=0.7, metadata={"env": "MIN_SIMILARITY"})
@@ -145,6 +148,7 @@ class Config:
     ENGINE_DTYPES = ("bf16", "fp16", "fp8")
     LLM_WEIGHT_DTYPES = ("bf16", "fp8")
     KV_CACHE_DTYPES = ("bf16", "fp8")
+    INDEX_DTYPES = ("bf16", "fp8")
 
     def validate_engine(self) -> "Config":
         """Startup check of the engine keys whose wrong value would otherwise silently run a
@@ -167,6 +171,12 @@ class Config:
         if self.kv_cache_dtype == "fp8" and self.tp_size > 1:
             # the per-head quantisation is shard-independent, but no TP test covers the combination
             raise ValueError("KV_CACHE_DTYPE=fp8 needs TP_SIZE=1")
+        if self.index_dtype not in self.INDEX_DTYPES:
+            raise ValueError(f"INDEX_DTYPE={self.index_dtype!r} is not supported "
+                             f"(choose one of {', '.join(self.INDEX_DTYPES)})")
+        if self.index_dtype == "fp8" and self.index_kind != "flat":
+            # IVFFlat permutes and trains on the bf16 rows; there is no fp8 list store
+            raise ValueError("INDEX_DTYPE=fp8 needs INDEX_KIND=flat")
         if self.search_transport not in ("plane", "rccl"):
             raise ValueError(f"SEARCH_TRANSPORT={self.search_transport!r} is not supported (plane | rccl)")
         if self.search_transport == "rccl" and self.tp_size > 1:

@@ -43,7 +43,7 @@ class Engine:
                  ivf_lists: int = 100, ivf_probes: int = 1, load_llm: bool = True, load_encoder: bool = True,
                  use_graphs: bool = True, embed_max_tokens: int = 65536, enc_dtype: str = "bf16",
                  share_prefix: bool = True, overlap_waves: bool = False, kv_cache_gb: float = 0.0,
-                 llm_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16"):
+                 llm_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16", index_dtype: str = "bf16"):
         self.device = torch.device(device)
         self.lock = threading.RLock()      # the decoder / generator (one GPU thread drives it)
         self.enc_lock = threading.RLock()  # the encoder: the fast embed lane and the batcher share it
@@ -81,7 +81,9 @@ class Engine:
                                  seed=seed, eos=sorted(self.chat.eos_ids), use_graphs=use_graphs,
                                  share_prefix=share_prefix)
         from ..index import make_index
-        self.index = make_index(index_kind, self.enc_cfg.hidden, self.device, lists=ivf_lists, probes=ivf_probes)
+        # index_dtype "fp8": flat-index rows as e4m3 codes + a scale per row (dim + 4 bytes instead of 2 dim)
+        self.index = make_index(index_kind, self.enc_cfg.hidden, self.device, lists=ivf_lists, probes=ivf_probes,
+                                dtype=index_dtype)
         self._prefix_cache: dict[str, list[int]] = {}
         self.stats = {"embed_texts": 0, "embed_tokens": 0, "embed_s": 0.0, "embed_truncated_texts": 0,
                       "embed_truncated_tokens": 0}

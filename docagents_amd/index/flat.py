@@ -7,6 +7,13 @@ filtered query reads only the rows it can match (exact, filter-before-top-k sema
 post-filters). Unfiltered / wide queries run the MFMA dense scan with a doc bitmap.
 
 Capacity grows geometrically; at 288 GB per GPU a 768-d bf16 shard holds ~180M rows.
+
+``dtype="fp8"`` (INDEX_DTYPE=fp8) stores every row as ``dim`` OCP e4m3 codes plus one fp32
+power-of-two scale (the smallest 2^e with amax / 2^e <= 448, 1 for an all-zero row: the KV cache's
+rule): ``dim + 4`` bytes per row instead of ``2 * dim``, ~370M 768-d rows per card. Incoming vectors
+are cast to bf16 and quantised straight into place; queries stay bf16 and a score is
+``scale[row] * sum(code_i * q_i)`` in fp32, so the fp8 index returns exactly the search of the bf16
+matrix ``codes * scale``. Scores move by up to ~0.007 against the unquantised rows (README).
 """
 from __future__ import annotations
 
@@ -31,15 +38,30 @@ class DocEntry:
 class FlatIndex:
     kind = "flat"
 
-    def __init__(self, dim: int, device="cuda", capacity: int = 1024, dtype=torch.bfloat16):
+    def __init__(self, dim: int, device="cuda", capacity: int = 1024, dtype="bf16"):
         self.dim = dim
         self.device = torch.device(device)
         self.ops = get_ops(self.device)
-        self.X = torch.zeros((max(64, capacity), dim), dtype=dtype, device=self.device)
-        self.slots_t = torch.full((self.X.shape[0],), -1, dtype=torch.int32, device=self.device)
+        if dtype == "bf16":
+            dtype = torch.bfloat16
+        if dtype != "fp8" and not isinstance(dtype, torch.dtype):
+            raise ValueError(f"unknown index dtype {dtype!r} (bf16 | fp8)")
+        self.dtype = "fp8" if dtype == "fp8" else "bf16"
+        cap = max(64, capacity)
+        if self.dtype == "fp8":
+            if self.device.type == "cuda" and dim not in self.ops.DENSE8_DIMS:
+                # no slower fp8 scan stands behind the streaming one
+                raise ValueError(f"fp8 index: dim {dim} is not one the fp8 dense scan is built for "
+                                 f"{self.ops.DENSE8_DIMS}")
+            self.codes = torch.zeros((cap, dim), dtype=torch.uint8, device=self.device)  # e4m3 bits
+            # padded to whole groups of 4 rows (the scan loads a tile's scales 16 B at a time)
+            self.scale = torch.ones(_pad4(cap), dtype=torch.float32, device=self.device)
+        else:
+            self.X = torch.zeros((cap, dim), dtype=dtype, device=self.device)
+        self.slots_t = torch.full((cap,), -1, dtype=torch.int32, device=self.device)
         self.n = 0
-        self.ids = np.zeros(self.X.shape[0], dtype=np.int64)     # external chunk id per row
-        self.ids_t = torch.zeros(self.X.shape[0], dtype=torch.int64, device=self.device)  # device mirror
+        self.ids = np.zeros(cap, dtype=np.int64)     # external chunk id per row
+        self.ids_t = torch.zeros(cap, dtype=torch.int64, device=self.device)  # device mirror
         self.docs: dict[str, DocEntry] = {}
         self.slot_docs: list[str | None] = []
         self.lock = threading.RLock()
@@ -96,12 +118,20 @@ class FlatIndex:
 
     # ----------------------------------------------------------------- mutation
     def _grow(self, need: int):
-        cap = self.X.shape[0]
+        cap = self.slots_t.shape[0]
         if need <= cap:
             return
         new = max(need, int(cap * 1.5) + 64)
-        X = torch.zeros((new, self.dim), dtype=self.X.dtype, device=self.device)
-        X[:self.n] = self.X[:self.n]
+        if self.dtype == "fp8":
+            codes = torch.zeros((new, self.dim), dtype=torch.uint8, device=self.device)
+            codes[:self.n] = self.codes[:self.n]
+            scale = torch.ones(_pad4(new), dtype=torch.float32, device=self.device)
+            scale[:self.n] = self.scale[:self.n]
+            rows_old = (self.codes, self.scale)
+        else:
+            X = torch.zeros((new, self.dim), dtype=self.X.dtype, device=self.device)
+            X[:self.n] = self.X[:self.n]
+            rows_old = (self.X,)
         s = torch.full((new,), -1, dtype=torch.int32, device=self.device)
         s[:self.n] = self.slots_t[:self.n]
         ids = np.zeros(new, dtype=np.int64)
@@ -112,9 +142,26 @@ class FlatIndex:
             # the copies above read the old buffers on this stream: the allocator must not hand
             # them out again (to an allocation on their own stream) before those copies ran
             st = torch.cuda.current_stream(self.device)
-            for old in (self.X, self.slots_t, self.ids_t):
+            for old in (*rows_old, self.slots_t, self.ids_t):
                 old.record_stream(st)
-        self.X, self.slots_t, self.ids, self.ids_t = X, s, ids, ids_t
+        if self.dtype == "fp8":
+            self.codes, self.scale = codes, scale
+        else:
+            self.X = X
+        self.slots_t, self.ids, self.ids_t = s, ids, ids_t
+
+    def _store(self, s0: int, vecs: torch.Tensor):
+        """Rows [s0, s0 + n) <- vecs. fp8: cast to bf16 first (what the WAL logs, so a replay
+        reproduces the same codes), then quantised straight into place."""
+        if self.dtype == "fp8":
+            x = vecs.to(device=self.device, dtype=torch.bfloat16).contiguous()
+            self.ops.index_quant_rows(x, self.codes, self.scale, s0)
+        else:
+            self.X[s0:s0 + int(vecs.shape[0])] = vecs.to(device=self.device, dtype=self.X.dtype)
+
+    def _rows(self):
+        """The live rows as the scans take them: bf16 [n, d], or the codes [n, d] (with self.scale)."""
+        return self.codes[:self.n] if self.dtype == "fp8" else self.X[:self.n]
 
     def doc_slot(self, doc_id: str) -> int:
         e = self.docs.get(doc_id)
@@ -136,7 +183,7 @@ class FlatIndex:
             slot = self.doc_slot(doc_id)
             s0 = self.n
             self._grow(s0 + n)
-            self.X[s0:s0 + n] = vecs.to(device=self.device, dtype=self.X.dtype)
+            self._store(s0, vecs)
             self.slots_t[s0:s0 + n] = slot
             self.ids[s0:s0 + n] = np.asarray(ids, dtype=np.int64)
             self.ids_t[s0:s0 + n] = h2d(self.ids[s0:s0 + n], self.device)
@@ -152,7 +199,7 @@ class FlatIndex:
             n = int(vecs.shape[0])
             s0 = self.n
             self._grow(s0 + n)
-            self.X[s0:s0 + n] = vecs.to(device=self.device, dtype=self.X.dtype)
+            self._store(s0, vecs)
             self.ids[s0:s0 + n] = ids
             self.ids_t[s0:s0 + n] = h2d(np.asarray(ids, dtype=np.int64), self.device)
             slots = np.empty(n, dtype=np.int32)
@@ -233,12 +280,12 @@ class FlatIndex:
         """q [Q, d] unit-norm -> (scores fp32 [Q, k], row idx int32 [Q, k]) on device; -inf / -1 padding.
         doc_filters: per-query list of document ids (None = all documents)."""
         Q = q.shape[0]
-        q = q.to(device=self.device, dtype=self.X.dtype).contiguous()
+        q = q.to(device=self.device, dtype=torch.bfloat16 if self.dtype == "fp8" else self.X.dtype).contiguous()
         with self.reading():
             if self.n == 0 or Q == 0:
                 return (torch.full((Q, k), float("-inf"), device=self.device),
                         torch.full((Q, k), -1, dtype=torch.int32, device=self.device))
-            X = self.X[:self.n]
+            X = self._rows()
             if doc_filters is None:
                 return self._dense(X, q, k, min_sim, self.slots_t[:self.n])
             ranges, off, maxrows = self._ranges_for(doc_filters)
@@ -250,11 +297,13 @@ class FlatIndex:
                 return self._dense(X, q, k, min_sim, self.slots_t[:self.n], doc_filters)
             rt = h2d(np.asarray(ranges, dtype=np.int32).reshape(-1, 2), self.device)
             ot = h2d(np.asarray(off, dtype=np.int32), self.device)
+            if self.dtype == "fp8":
+                return self.ops.topk_ranges8(X, self.scale, q, rt, ot, k, min_sim, max_rows=maxrows)
             return self.ops.topk_ranges(X, q, rt, ot, k, min_sim, max_rows=maxrows)
 
     def _dense(self, X, q, k, min_sim, slots, doc_filters=None):
         """MFMA dense scan; doc filter as a bitmap over local doc slots. Removed rows (slot -1) map to
-        a guard slot whose bit is never set."""
+        a guard slot whose bit is never set. fp8: ``X`` is the codes and the scan takes self.scale."""
         Q = q.shape[0]
         nslots = len(self.slot_docs)
         guard = nslots
@@ -279,6 +328,8 @@ class FlatIndex:
                         bm[i, e.slot >> 5] |= np.uint32(1 << (e.slot & 31))
         bitmap = h2d(bm.view(np.int32), self.device)
         slots = torch.where(slots < 0, torch.full_like(slots, guard), slots).contiguous()
+        if self.dtype == "fp8":
+            return self.ops.topk_dense8(X, self.scale, q, k, min_sim, slots=slots, bitmap=bitmap)
         return self.ops.topk_dense(X, q, k, min_sim, slots=slots, bitmap=bitmap)
 
     def gather_ids(self, rows: torch.Tensor) -> torch.Tensor:
@@ -321,18 +372,38 @@ class FlatIndex:
             for d, e in self.docs.items():
                 for a, b in e.ranges:
                     live.append((d, a, b))
-            return {"dim": self.dim, "live": live, "X": self.X[:self.n].cpu(), "ids": self.ids[:self.n].copy()}
+            return {"dim": self.dim, "dtype": self.dtype, "live": live, "X": self.dense_rows().cpu(),
+                    "ids": self.ids[:self.n].copy()}
+
+    def dense_rows(self, sel: torch.Tensor | None = None) -> torch.Tensor:
+        """The stored rows [n, d] (or the rows ``sel``); fp8: dequantised to bf16, which is exact."""
+        if self.dtype != "fp8":
+            return self.X[:self.n] if sel is None else self.X.index_select(0, sel)
+        codes = self.codes[:self.n] if sel is None else self.codes.index_select(0, sel)
+        scale = self.scale[:self.n] if sel is None else self.scale.index_select(0, sel)
+        return (codes.view(torch.float8_e4m3fn).float() * scale[:, None]).to(torch.bfloat16)
 
     def nbytes(self) -> int:
+        if self.dtype == "fp8":
+            return self.n * (self.dim + 4)
         return self.n * self.dim * self.X.element_size()
 
 
-def bytes_per_row(dim: int) -> int:
+def bytes_per_row(dim: int, dtype: str = "bf16") -> int:
+    """bf16: the row + its int32 doc slot; fp8: the codes + the row's fp32 scale."""
+    if dtype == "fp8":
+        return dim + 4
+    if dtype != "bf16":
+        raise ValueError(f"unknown index dtype {dtype!r} (bf16 | fp8)")
     return dim * 2 + 4
 
 
-def rows_for_budget(dim: int, gbytes: float) -> int:
-    return int(gbytes * 1e9 // bytes_per_row(dim))
+def rows_for_budget(dim: int, gbytes: float, dtype: str = "bf16") -> int:
+    return int(gbytes * 1e9 // bytes_per_row(dim, dtype))
+
+
+def _pad4(n: int) -> int:
+    return (n + 3) // 4 * 4
 
 
 def _pad64(n: int) -> int:

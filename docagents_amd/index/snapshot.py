@@ -19,11 +19,18 @@ def save_index(index, path: str, extra_meta: dict | None = None, durable: bool =
         sel, docs = index.live_rows_by_doc()
         docs = [[d, n] for d, n in docs]
         selt = torch.from_numpy(sel.astype(np.int64)).to(index.device)
-        tensors = {"X": index.X.index_select(0, selt).cpu().contiguous(),
-                   "ids": torch.from_numpy(index.ids[sel].copy())}
+        fp8 = getattr(index, "dtype", "bf16") == "fp8"
+        if fp8:  # the codes (e4m3 bits as uint8) and the per-row scales, as stored
+            tensors = {"codes": index.codes.index_select(0, selt).cpu().contiguous(),
+                       "scale": index.scale.index_select(0, selt).cpu().contiguous()}
+        else:
+            tensors = {"X": index.X.index_select(0, selt).cpu().contiguous()}
+        tensors["ids"] = torch.from_numpy(index.ids[sel].copy())
         if getattr(index, "centroids", None) is not None:
             tensors["centroids"] = index.centroids.cpu().contiguous()
         meta = {"dim": str(index.dim), "kind": index.kind, "docs": json.dumps(docs)}
+        if fp8:  # a snapshot without ``dtype`` is bf16
+            meta["dtype"] = "fp8"
         meta.update({k: str(v) for k, v in (extra_meta or {}).items()})
     tmp = path + ".tmp"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -58,9 +65,22 @@ def load_index(index, path: str) -> int:
     if int(meta["dim"]) != index.dim:
         raise ValueError(f"snapshot dim {meta['dim']} != index dim {index.dim}")
     docs = json.loads(meta["docs"])
-    X, ids = t["X"], t["ids"].numpy()
+    ids = t["ids"].numpy()
+    fp8 = meta.get("dtype", "bf16") == "fp8"
+    if meta.get("dtype", "bf16") not in ("bf16", "fp8"):
+        raise ValueError(f"snapshot dtype {meta['dtype']!r} is not supported (bf16 | fp8)")
+    # either snapshot kind into either index kind: fp8 rows dequantise exactly (codes * scale is a
+    # bf16 value), bf16 rows are quantised by add_bulk
+    X = (t["codes"].view(torch.float8_e4m3fn).float() * t["scale"][:, None]).to(torch.bfloat16) if fp8 else t["X"]
     with index.writing():
+        s0 = len(index)
         index.add_bulk([d for d, _ in docs], [n for _, n in docs], ids, X)
+        if fp8 and getattr(index, "dtype", "bf16") == "fp8":
+            # keep the saved codes bit for bit (re-quantising the dequantised row may pick a smaller
+            # scale with larger codes: the same values, other bits)
+            n = X.shape[0]
+            index.codes[s0:s0 + n] = t["codes"].to(index.device)
+            index.scale[s0:s0 + n] = t["scale"].to(index.device)
         if "centroids" in t and hasattr(index, "_build_lists"):
             index.centroids = t["centroids"].to(index.device)
             index._build_lists()

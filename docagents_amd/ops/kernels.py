@@ -83,6 +83,11 @@ _SIGS = {
     "da_topk_ranges": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                        c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "da_topk_merge": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "da_index_quant_rows": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "da_topk_dense_stream8": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float,
+                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "da_topk_ranges8": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                        c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "da_kmeans_accum": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "da_sample_partial": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_uint, c_uint, c_void_p, c_void_p, c_void_p],
     "da_sample_chunked": [c_void_p, c_int, c_int, c_int, c_float, c_uint, c_uint] + [c_void_p] * 10
@@ -141,6 +146,8 @@ def lib() -> ctypes.CDLL:
         L.da_topk_dense_ws.restype = c_size_t
         L.da_topk_stream_ws.argtypes = [c_int, c_int, c_int, c_int]
         L.da_topk_stream_ws.restype = c_size_t
+        L.da_topk_dense_stream8_ws.argtypes = [c_int, c_int, c_int, c_int]
+        L.da_topk_dense_stream8_ws.restype = c_size_t
         _LIB = L
         return L
 
@@ -1030,6 +1037,102 @@ def topk_ranges(X, Qv, ranges, range_off, K: int, thr: float, max_rows: int, slo
     _check(lib().da_topk_ranges(_ptr(X), d, _ptr(slots), _ptr(Qv), Q, _ptr(ranges), _ptr(range_off), _ptr(bitmap),
                                 W, float(thr), K, splits, rows_per_split, _ptr(ws), _ptr(out_s), _ptr(out_i),
                                 _stream()), "topk_ranges")
+    return out_s, out_i
+
+
+# ------------------------------------------------------------------- fp8 vector index (INDEX_DTYPE=fp8)
+# rows as e4m3 codes [N, d] (uint8 or float8_e4m3fn) + one fp32 power-of-two scale per row
+# (quant_weight_fp8_pow2's rule); queries stay bf16. See csrc/vecsearch8.hip.
+DENSE8_DIMS = (128, 384, 768, 1024)  # the widths the fp8 dense scan is built for
+
+
+def _codes_cuda(codes, scale, rows: int):
+    _req(codes.is_cuda and codes.dtype in (FP8, torch.uint8) and codes.dim() == 2 and codes.is_contiguous(),
+         "codes must be contiguous e4m3 / uint8 [N, d] on GPU")
+    _req(scale.is_cuda and scale.dtype == torch.float32 and scale.dim() == 1 and scale.is_contiguous()
+         and scale.numel() >= rows, "scale must be contiguous fp32 [>= N] on GPU")
+    _req(codes.data_ptr() % 16 == 0, "codes alignment")
+
+
+def index_quant_rows(X, codes, scale, row0: int = 0):
+    """bf16 rows X [n, d] -> codes[row0:row0 + n] (uint8 / e4m3 [cap, d]) and scale[row0:row0 + n]
+    (fp32 [cap]), bit-identical to reference.quant_weight_fp8_pow2(X). Nothing else is written."""
+    _bf16_cuda(X, "X")
+    _req(X.dim() == 2 and X.is_contiguous() and X.data_ptr() % 8 == 0, "X must be contiguous [n, d]")
+    n, d = X.shape
+    row0 = int(row0)
+    _codes_cuda(codes, scale, row0 + n)
+    _req(d % 4 == 0 and codes.shape[1] == d, "d % 4 == 0 and codes [cap, d]")
+    _req(0 <= row0 and row0 + n <= codes.shape[0], "rows [row0, row0 + n) outside codes")
+    _check(lib().da_index_quant_rows(_ptr(X), n, d, _ptr(codes), _ptr(scale), row0, _stream()), "index_quant_rows")
+    return codes, scale
+
+
+def _filter_args(N, Q, slots, bitmap):
+    W = 0
+    if slots is not None:
+        _i32(slots, "slots")
+        _req(slots.numel() >= N, "slots length")
+    if bitmap is not None:
+        _req(slots is not None, "bitmap needs slots")
+        _req(bitmap.dtype == torch.int32 and bitmap.is_contiguous() and bitmap.shape[0] == Q, "bitmap [Q, W] int32")
+        W = bitmap.shape[1]
+    return W
+
+
+def topk_dense8(codes, scale, Qv, K: int, thr: float, slots=None, bitmap=None):
+    """topk_dense over fp8 rows: exact top-K of Qv @ (codes * scale)^T (fp32 accumulation) per query
+    with threshold and optional doc-slot bitmap. d must be one of DENSE8_DIMS: there is no slower fp8
+    kernel behind the streaming scan (more than 256 queries run as passes of 256). The partitioning
+    is topk_dense's."""
+    _bf16_cuda(Qv, "Qv")
+    N, d = codes.shape
+    Q = Qv.shape[0]
+    _codes_cuda(codes, scale, N)
+    _req(Qv.dim() == 2 and Qv.is_contiguous() and Qv.shape[1] == d and Qv.data_ptr() % 16 == 0, "Qv layout")
+    _req(d in DENSE8_DIMS, f"fp8 dense scan: d must be one of {DENSE8_DIMS}, got {d}")
+    _req(1 <= K <= 32 and N > 0, "1 <= K <= 32, N > 0")
+    W = _filter_args(N, Q, slots, bitmap)
+    if Q > 256:  # the scan's batch limit (topk_dense's streaming path has the same): 256 queries per pass
+        parts = [topk_dense8(codes, scale, Qv[a:a + 256], K, thr, slots,
+                             None if bitmap is None else bitmap[a:a + 256]) for a in range(0, Q, 256)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+    n4 = (N + 3) // 4 * 4
+    if scale.numel() < n4 or scale.data_ptr() % 16:
+        # the scan reads the scales of a tile's 4-row groups with one aligned 16-B load
+        pad = torch.ones(n4, dtype=torch.float32, device=scale.device)
+        pad[:N] = scale[:N]
+        scale = pad
+    rpw = max(64, math.ceil(N / (256 * 16) / 16) * 16)
+    ws = _workspace(int(lib().da_topk_dense_stream8_ws(N, Q, K, rpw)), codes.device)
+    out_s = torch.empty((Q, K), dtype=torch.float32, device=codes.device)
+    out_i = torch.empty((Q, K), dtype=torch.int32, device=codes.device)
+    _check(lib().da_topk_dense_stream8(_ptr(codes), _ptr(scale), N, d, _ptr(slots), _ptr(Qv), Q, _ptr(bitmap), W,
+                                       float(thr), K, rpw, _ptr(ws), _ptr(out_s), _ptr(out_i), _stream()),
+           "topk_dense_stream8")
+    return out_s, out_i
+
+
+def topk_ranges8(codes, scale, Qv, ranges, range_off, K: int, thr: float, max_rows: int, slots=None, bitmap=None,
+                 rows_per_split: int = 512):
+    """topk_ranges over fp8 rows. ranges int32 [R, 2] (inside [0, N)), range_off int32 [Q+1]; max_rows =
+    max total rows of any query (host int) — sets the split count."""
+    _bf16_cuda(Qv, "Qv")
+    N, d = codes.shape
+    Q = Qv.shape[0]
+    _codes_cuda(codes, scale, N)
+    _req(Qv.dim() == 2 and Qv.is_contiguous() and Qv.shape[1] == d and Qv.data_ptr() % 16 == 0, "Qv layout")
+    _req(d % 16 == 0 and d <= 4096 and 1 <= K <= 32, "d / K limits")
+    _i32(ranges, "ranges"); _i32(range_off, "range_off")
+    _req(range_off.numel() == Q + 1, "range_off length")
+    W = _filter_args(N, Q, slots, bitmap)
+    splits = max(1, math.ceil(max_rows / rows_per_split))
+    ws = _workspace(splits * Q * K * 8, codes.device)
+    out_s = torch.empty((Q, K), dtype=torch.float32, device=codes.device)
+    out_i = torch.empty((Q, K), dtype=torch.int32, device=codes.device)
+    _check(lib().da_topk_ranges8(_ptr(codes), _ptr(scale), d, _ptr(slots), _ptr(Qv), Q, _ptr(ranges),
+                                 _ptr(range_off), _ptr(bitmap), W, float(thr), K, splits, rows_per_split, _ptr(ws),
+                                 _ptr(out_s), _ptr(out_i), _stream()), "topk_ranges8")
     return out_s, out_i
 
 

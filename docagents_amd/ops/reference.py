@@ -494,6 +494,35 @@ def quant_weight_fp8_pow2(w):
     return (wf / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), s.contiguous()
 
 
+# ----------------------------------------------------------------------------------- fp8 vector index
+# codes [N, d] (uint8 / float8_e4m3fn) + scale fp32 [N]: every row is quant_weight_fp8_pow2 of the
+# bf16 row, so codes * scale is exact in bf16 and the fp8 searches ARE the bf16 searches of that matrix.
+DENSE8_DIMS = (128, 384, 768, 1024)
+
+
+def index_dequant(codes, scale):
+    """bf16 [N, d]: codes * scale (exact)."""
+    c = codes.view(torch.float8_e4m3fn) if codes.dtype == torch.uint8 else codes
+    return (c.float() * scale[:c.shape[0], None].float()).to(torch.bfloat16)
+
+
+def index_quant_rows(X, codes, scale, row0=0):
+    n = X.shape[0]
+    q, s = quant_weight_fp8_pow2(X.to(torch.bfloat16))
+    codes.view(torch.uint8)[row0:row0 + n] = q.view(torch.uint8)
+    scale[row0:row0 + n] = s
+    return codes, scale
+
+
+def topk_dense8(codes, scale, Qv, K, thr, slots=None, bitmap=None, **_):
+    return topk_dense(index_dequant(codes, scale), Qv, K, thr, slots=slots, bitmap=bitmap)
+
+
+def topk_ranges8(codes, scale, Qv, ranges, range_off, K, thr, max_rows=None, slots=None, bitmap=None, **_):
+    return topk_ranges(index_dequant(codes, scale), Qv, ranges, range_off, K, thr, max_rows=max_rows, slots=slots,
+                       bitmap=bitmap)
+
+
 # ----------------------------------------------------------------------------------- fp8 KV cache
 # codes [slots, Hkv, max_seq, D] float8_e4m3fn + scales [slots, Hkv, max_seq] fp32: every cached row
 # is quant_weight_fp8_pow2 of the bf16 row (power-of-two scale: code * scale is exact in bf16).
