@@ -247,7 +247,7 @@ class KVCache:
         return cfg.layers * 2 * slots * (cfg.kv_heads // tp_size) * max_seq * row
 
 
-WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMV chain
+WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMVs and the 2..32-row gemm_dk steps
 
 
 class LlamaDecoder:
@@ -301,9 +301,10 @@ class LlamaDecoder:
     def _quantise_weights_fp8(self):
         """weight_dtype="fp8": the model IS the quantised model. Every matmul weight is quantised per
         output row to e4m3 with a power-of-two scale and the bf16 tensor is replaced by the dequantised
-        values (exact in bf16), so prefill and batched decode compute the same model the batch-1 fp8
-        GEMVs stream at half the bytes. The fp8 copy ({name}_q8 [N, K] e4m3, {name}_s8 [N] fp32) is
-        kept only for the products ops.gemm_w8 accepts; the embedding and the norm gains stay bf16."""
+        values (exact in bf16), so prefill and the wider decode steps compute the same model the batch-1
+        fp8 GEMVs and the 2..32-row fp8 gemm_dk steps stream at half the bytes. The fp8 copy ({name}_q8
+        [N, K] e4m3, {name}_s8 [N] fp32) is kept only for the products ops.gemm_w8 or ops.gemm_dk_w8
+        accepts; the embedding and the norm gains stay bf16."""
         o = self.ops
         prods = [(L, k, e) for L in self.w["layers"]
                  for k, e in (("wqkv", EPI_NONE), ("wo", EPI_RESID), ("w_gu", EPI_SWIGLU), ("w_down", EPI_RESID))]
@@ -312,16 +313,32 @@ class LlamaDecoder:
             w = d[k]
             q, s = o.quant_weight_fp8_pow2(w)
             d[k] = (q.float() * s[:, None]).to(w.dtype).contiguous()
-            if o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi):
+            if o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi) or o.dk_w8_fusable(2, w.shape[0], w.shape[1], epi):
                 d[k + "_q8"], d[k + "_s8"] = q, s
             del w, q, s
 
     def _gemm1(self, d, name, a, **kw):
         """The product a @ d[name]^T of a decode / prefill layer: the fp8 GEMV when ``a`` is one row
-        and the weight has an fp8 copy (weight_dtype="fp8"), today's bf16 ops.gemm otherwise."""
-        if self.weight_dtype == "fp8" and a.shape[0] == 1 and (name + "_q8") in d:
+        and the GEMV takes the weight's fp8 copy (weight_dtype="fp8"; a copy may be kept for gemm_dk_w8
+        alone, e.g. K = 256), today's bf16 ops.gemm otherwise."""
+        if self.weight_dtype == "fp8" and a.shape[0] == 1 and (name + "_q8") in d and self.ops.gemv_w8_fusable(
+                1, d[name].shape[0], d[name].shape[1], kw.get("epi", EPI_NONE)):
             return self.ops.gemm_w8(a, d[name + "_q8"], d[name + "_s8"], **kw)
         return self.ops.gemm(a, d[name], **kw)
+
+    def _dk_w8(self, d, name, B: int, epi: int) -> bool:
+        """True when the B-row gemm_dk product on d[name] streams the fp8 copy (ops.gemm_dk_w8)."""
+        w = d[name]
+        return (self.weight_dtype == "fp8" and (name + "_q8") in d
+                and self.ops.dk_w8_fusable(B, w.shape[0], w.shape[1], epi))
+
+    def _gemm_dk1(self, d, name, a, epi: int = EPI_NONE, **kw):
+        """The product a @ d[name]^T of a gemm_dk decode layer: gemm_dk_w8 on the fp8 copy at 2..32
+        rows where the weight has one (weight_dtype="fp8"), today's ops.gemm_dk on the bf16 tensor
+        otherwise."""
+        if self._dk_w8(d, name, a.shape[0], epi):
+            return self.ops.gemm_dk_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
+        return self.ops.gemm_dk(a, d[name], epi=epi, **kw)
 
     def _gain(self, g):
         """The gain a fused batch-1 GEMV norm streams: none once the gains are folded."""
@@ -526,16 +543,17 @@ class LlamaDecoder:
         c, o = self.cfg, self.ops
         layers = self.w["layers"]
         sa, sb = st.ssq
-        parts = o.dk_parts(c.hidden, x.shape[0])
+        dk = self._gemm_dk1
+        parts = o.dk_parts(c.hidden, x.shape[0])  # both kernels tile a residual producer alike: one part count
         a_in, norm = o.rmsnorm(x, layers[0]["ln_attn"], c.eps, out=st.h), None
         for li, L in enumerate(layers):
-            qkv = o.gemm_dk(a_in, L["wqkv"], out=st.qkv, norm_in=norm)
+            qkv = dk(L, "wqkv", a_in, out=st.qkv, norm_in=norm)
             a = self._decode_attn(qkv, li, st)
-            o.gemm_dk(a, L["wo"], epi=EPI_RESID, resid=x, out=x, ssq_out=sa)               # x += o
-            g = o.gemm_dk(x, L["w_gu"], epi=EPI_SWIGLU, norm_in=(sa, parts, c.eps))        # norm(x) -> gate/up
-            o.gemm_dk(g, L["w_down"], epi=EPI_RESID, resid=x, out=x, ssq_out=sb)           # x += mlp
+            dk(L, "wo", a, epi=EPI_RESID, resid=x, out=x, ssq_out=sa)                      # x += o
+            g = dk(L, "w_gu", x, epi=EPI_SWIGLU, norm_in=(sa, parts, c.eps))               # norm(x) -> gate/up
+            dk(L, "w_down", g, epi=EPI_RESID, resid=x, out=x, ssq_out=sb)                  # x += mlp
             a_in, norm = x, (sb, parts, c.eps)
-        o.gemm_dk(x, self.w["lm_head"], out=st.logits, norm_in=norm)                      # final norm deferred
+        dk(self.w, "lm_head", x, out=st.logits, norm_in=norm)                             # final norm deferred
         o.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
                  active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
         return st.tokens

@@ -22,17 +22,7 @@
 // of its bf16 output slice (ssq_out [parts][64]); the consumer reads x itself as A and scales each A
 // fragment by inv[m] = rsqrt(sum_parts / norm_k + eps) before the MFMA (bf16-rounded exactly like
 // the rmsnorm kernel's output; the RMSNorm gains are folded into W at load, models/llama.py).
-#include "gemm.h"
-
-struct DkArgs {
-  const bf16_t* A; const bf16_t* W; bf16_t* C;
-  const bf16_t* bias; const bf16_t* resid;
-  const float* ssq_in;  // NORM: [ssq_parts][64] partial sums of squares of A's rows
-  float* ssq_out;       // EPI_RESID (nullable): [gridDim.x][64] sums of squares of this tile's output rows
-  int M, N, K, lda, ldc, ldr, ssq_parts, norm_k;
-  float eps;
-  int rb;  // row blocks of BM rows: 1, or 2 (M > BM; workgroup pairs share an XCD)
-};
+#include "gemm_dk.h"
 
 template <int BM, int BN, int EPI, bool NORM, int PF>
 __global__ void __launch_bounds__(256)
@@ -260,14 +250,6 @@ gemm_dk_kernel(DkArgs p) {
       }
     }
   }
-}
-
-// Output-tile width: the widest of 64 / 32 / 16 W rows that still gives >= 192 workgroups (SwiGLU
-// needs whole 32-row gate/up groups).
-static int dk_bn(int N, int epi) {
-  if (N / 64 >= 192) return 64;
-  if (N / 32 >= 192 || epi == EPI_SWIGLU) return 32;
-  return 16;
 }
 
 // Chunks in flight per workgroup: ~64 KB of W (128 / BN chunks of BN x 512 B) within ~160 VGPRs of

@@ -43,7 +43,7 @@ WIDE_N = 8192    # 65..128 rows: weight rows from which the 64x128 tile runs uns
 
 
 class GemmPlan(NamedTuple):
-    family: str    # "gemv" | "dk" | "dk_splitk" | "tile" | "gemm8p" | "gemm4w"
+    family: str    # "gemv" | "dk" | "dk_splitk" | "dk_w8" | "tile" | "gemm8p" | "gemm4w"
     tile: int
     splits: int
     ws_bytes: int  # fp32 split-K partials: splits * M * N * 4, 0 where the launch needs no workspace
@@ -169,6 +169,25 @@ def plan_dk(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
         splits = dk_splits(N, K)
         return GemmPlan("dk_splitk", TILE_DK, splits, splits * M * N * 4)
     return GemmPlan("dk", TILE_DK, 1, 0)
+
+
+# gemm_dk on the decoder's e4m3 weight copy (csrc/gemm_dk_w8.hip): 2..32 rows only; 33..64 rows (the
+# split-K route) and everything wider stay on the bf16 tensors
+DK_W8_MAX_M = 32
+
+
+def dk_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
+    """True when a decode step runs the product on gemm_dk_w8 (fp8 weights) instead of gemm_dk: every
+    shape the kernel takes at 2..32 rows (one row is the fp8 GEMV's, gemv_w8_fusable). fp8 beat the
+    bf16 gemm_dk on all five Phi-3-mini products at 4, 16 and 32 rows (0.67-0.91x, profiles/w8dk/README.md),
+    so no shape is held back. An EPI_RESID launch tiles like gemm_dk and writes dk_parts(N) parts."""
+    return (2 <= M <= DK_W8_MAX_M and K % 256 == 0 and N % 16 == 0
+            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
+
+
+def plan_dk_w8(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
+    """gemm_dk_w8()'s launch: always da_gemm_dk_w8, one launch, no split-K, no workspace."""
+    return GemmPlan("dk_w8", TILE_DK, 1, 0)
 
 
 def plan_resid_norm(M: int, N: int, K: int, tile: int = 0, splits: int = 0) -> GemmPlan:

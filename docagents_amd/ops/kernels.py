@@ -18,8 +18,8 @@ from pathlib import Path
 import torch
 
 from . import gemm_plan
-from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, gemv_fusable,  # noqa: F401 - re-exported
-                        gemv_w8_fusable)
+from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: F401 - re-exported
+                        gemv_fusable, gemv_w8_fusable)
 
 _LIB = None
 _LOCK = threading.Lock()
@@ -67,6 +67,8 @@ _SIGS = {
     "da_gemm_dk": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                    c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "da_gemm_dk_parts": [c_int],
+    "da_gemm_dk_w8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                      c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "da_gemm_dk_splitk": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "da_decode_attn": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -441,6 +443,59 @@ def gemm_w8(a: torch.Tensor, wq: torch.Tensor, sw: torch.Tensor, bias=None, epi:
         return out
     _check(lib().da_gemv_w8(_ptr(a), _ptr(wq), _ptr(sw), _ptr(out), _ptr(bias), _ptr(resid), N, K, epi, _ptr(gamma),
                             float(eps), _stream()), "gemm_w8")
+    return out
+
+
+def gemm_dk_w8(a, wq, sw, epi: int = EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
+    """gemm_dk on e4m3 weights with fp32 row scales (1 <= M <= 32), one launch:
+    out = epi((rownorm(a) @ wq^T) * sw[None, :]). norm_in / ssq_out as gemm_dk (dk_parts(N, M) parts: a residual
+    producer tiles like gemm_dk's). Anything the kernel would refuse raises ValueError before any launch."""
+    _bf16_cuda(a, "a")
+    _req(wq.is_cuda and wq.dtype == FP8, f"wq must be float8_e4m3fn on GPU, got {wq.dtype}")
+    _req(a.dim() == 2 and wq.dim() == 2, "gemm_dk_w8 expects 2-D operands")
+    M, K = a.shape
+    N, K2 = wq.shape
+    _req(K == K2, f"K mismatch {K} vs {K2}")
+    _req(1 <= M <= gemm_plan.DK_W8_MAX_M and K >= 256 and K % 256 == 0 and N >= 16 and N % 16 == 0,
+         f"gemm_dk_w8 shape M={M} N={N} K={K}")
+    _req(epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0),
+         f"gemm_dk_w8 does not take epi={epi} at N={N}")
+    _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.stride(0) >= K, "a must be row-major, 16-B aligned rows")
+    _req(wq.is_contiguous(), "wq must be contiguous")
+    _req(sw.is_cuda and sw.dtype == torch.float32 and sw.is_contiguous() and sw.shape == (N,), "sw must be fp32 [N]")
+    _req(a.data_ptr() % 16 == 0 and wq.data_ptr() % 16 == 0 and sw.data_ptr() % 16 == 0,
+         "operands must be 16-B aligned")
+    nout = N // 2 if epi == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
+    _bf16_cuda(out, "out")
+    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         "bad out")
+    if bias is not None:
+        _bf16_cuda(bias, "bias")
+        _req(bias.numel() == N and bias.is_contiguous() and bias.data_ptr() % 16 == 0, "bias must be [N]")
+        _req(epi in (EPI_BIAS, EPI_RESID), "bias only with BIAS/RESID epilogues")
+    ldr = 0
+    if epi == EPI_RESID:
+        _req(resid is not None, "EPI_RESID needs resid")
+        _bf16_cuda(resid, "resid")
+        _req(resid.shape == (M, N) and resid.stride(1) == 1 and resid.stride(0) % 8 == 0
+             and resid.data_ptr() % 16 == 0, "bad resid")
+        ldr = resid.stride(0)
+    else:
+        resid = None
+    ssq, parts, eps = (None, 0, 0.0) if norm_in is None else norm_in
+    if ssq is not None:
+        _req(epi != EPI_RESID, "a residual producer takes no deferred norm")
+        _req(ssq.is_cuda and ssq.dtype == torch.float32 and ssq.is_contiguous() and parts >= 1
+             and ssq.numel() >= parts * 64 and ssq.data_ptr() % 16 == 0 and eps > 0, "bad ssq_in")
+    if ssq_out is not None:
+        _req(epi == EPI_RESID, "ssq_out needs the residual epilogue")
+        _req(ssq_out.is_cuda and ssq_out.dtype == torch.float32 and ssq_out.is_contiguous()
+             and ssq_out.numel() >= dk_parts(N, M) * 64, "bad ssq_out")
+    _check(lib().da_gemm_dk_w8(_ptr(a), a.stride(0), _ptr(wq), _ptr(sw), _ptr(out), out.stride(0), _ptr(bias),
+                               _ptr(resid), ldr, M, N, K, epi, _ptr(ssq), parts, K, float(eps), _ptr(ssq_out),
+                               _stream()), "gemm_dk_w8")
     return out
 
 

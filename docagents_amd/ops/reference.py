@@ -622,6 +622,20 @@ def gemm_dk(a, w, epi=EPI_NONE, bias=None, resid=None, out=None, norm_in=None, s
     return y
 
 
+def dk_w8_fusable(M, N, K, epi=EPI_NONE):
+    return (2 <= M <= 32 and K % 256 == 0 and N % 16 == 0
+            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
+
+
+def gemm_dk_w8(a, wq, sw, epi=EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
+    """gemm_dk_w8.hip: gemm_dk on the dequantised matrix wq * sw, held in fp32. With the decoder's
+    power-of-two scales those values are exact in bf16 and this is bit for bit gemm_dk on the bf16
+    matrix; an arbitrary fp32 scale is not rounded to bf16 here (the kernel does not round it either:
+    rounded weights moved a SwiGLU output with a cancelling up-sum by 0.06, twice the kernel tests' atol)."""
+    w = wq.float() * sw[:, None].float()
+    return gemm_dk(a, w, epi=epi, bias=bias, resid=resid, out=out, norm_in=norm_in, ssq_out=ssq_out)
+
+
 def gemm_resid_norm(a, w, resid, gamma, eps, out=None, h_out=None, bias=None):
     y = gemm(a, w, bias=bias, epi=EPI_RESID, resid=resid)
     (resid if out is None else out).copy_(y)
