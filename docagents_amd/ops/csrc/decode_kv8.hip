@@ -3,11 +3,12 @@
 //
 // Storage: every K row and every V row of one (token, kv head) — D values — is stored as D e4m3
 // codes plus ONE fp32 power-of-two scale: the smallest 2^e with amax / 2^e <= 448 (1 for an
-// all-zero row), the rule quant_weight_fp8_pow2 applies to weight rows. code * 2^e is exact in bf16.
+// all-zero row): fp8_pow2_scale (fp8.h). code * 2^e is exact in bf16.
 //   codes  [slots, Hkv, max_seq, D]  one byte each
 //   scales [slots, Hkv, max_seq]     fp32
 // A decode-attention launch streams (D + 4) bytes per cached row instead of 2 D.
 #include "decode_merge.h"
+#include "fp8.h"
 
 // ------------------------------------------------------------------------------------------
 // RoPE (in place on the q and k heads of qkv, the roundings of rope_cache_kernel) + quantisation of
@@ -52,18 +53,12 @@ rope_cache_kv8_kernel(bf16_t* __restrict__ qkv, const int* __restrict__ pos, con
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
   if (!(quant && act)) return;
-  // smallest 2^e with amax / 2^e <= 448 = 1.75 * 2^8: amax = f * 2^E, f in [1, 2) -> e = E - 8 (+ 1 if f > 1.75)
-  const unsigned ab = __float_as_uint(amax);
-  int e = (int)(ab >> 23) - 127 - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
-  e = max(e, -126);
-  if (amax == 0.f) e = 0;
-  const float sc = __uint_as_float((unsigned)(127 + e) << 23), inv = __uint_as_float((unsigned)(127 - e) << 23);
-  int code = __builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv, x[1] * inv, 0, false);
-  code = __builtin_amdgcn_cvt_pk_fp8_f32(x[2] * inv, x[3] * inv, code, true);
+  float sc, inv;
+  fp8_pow2_scale(amax, sc, inv);
   const int hk = (j - Hq) % Hkv;
   const bool isk = j < Hq + Hkv;
   const size_t row = ((size_t)s * Hkv + hk) * max_seq + p;
-  *(int*)((isk ? kq : vq) + row * D + l * 4) = code;
+  *(unsigned*)((isk ? kq : vq) + row * D + l * 4) = f32x4_fp8(x[0], x[1], x[2], x[3], inv);
   if (l == 0) (isk ? ksc : vsc)[row] = sc;
 }
 
@@ -95,18 +90,16 @@ kv8_dequant_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ 
   const size_t row = ((size_t)slot * Hkv + hk) * max_seq + p;
   const u32x4_t w = *(const u32x4_t*)(codes + row * D + c * 16);
   const float s = scale[row];
-  u32x4_t lo, hi;
+  unsigned b[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(w[e], false);
-    const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8(w[e], true);
-    const unsigned w0 = pack_bf2(a[0] * s, a[1] * s), w1 = pack_bf2(b[0] * s, b[1] * s);
-    if (e < 2) { lo[2 * e] = w0; lo[2 * e + 1] = w1; }
-    else { hi[2 * (e - 2)] = w0; hi[2 * (e - 2) + 1] = w1; }
+    const f32x4_t f = fp8x4_f32(w[e]);
+    b[2 * e] = pack_bf2(f[0] * s, f[1] * s);
+    b[2 * e + 1] = pack_bf2(f[2] * s, f[3] * s);
   }
   bf16_t* dst = out + ((size_t)hk * P + p) * D + c * 16;
-  *(u32x4_t*)dst = lo;
-  *(u32x4_t*)(dst + 8) = hi;
+  *(u32x4_t*)dst = u32x4_t{b[0], b[1], b[2], b[3]};
+  *(u32x4_t*)(dst + 8) = u32x4_t{b[4], b[5], b[6], b[7]};
 }
 
 DA_EXPORT int da_kv8_dequant(const void* codes, const void* scale, int slot, int slots, int Hkv, int P, int D,
@@ -222,8 +215,9 @@ decode_attn_kv8_kernel(const bf16_t* __restrict__ q, int ldq, const uint8_t* __r
       f32x2_t kf[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        kf[2 * e] = __builtin_amdgcn_cvt_pk_f32_fp8(kv[i][e], false);
-        kf[2 * e + 1] = __builtin_amdgcn_cvt_pk_f32_fp8(kv[i][e], true);
+        const f32x4_t f = fp8x4_f32(kv[i][e]);
+        kf[2 * e] = f.lo;
+        kf[2 * e + 1] = f.hi;
       }
 #pragma unroll
       for (int g = 0; g < G; ++g) {
@@ -283,8 +277,9 @@ decode_attn_kv8_kernel(const bf16_t* __restrict__ q, int ldq, const uint8_t* __r
       f32x2_t vf[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        vf[2 * e] = __builtin_amdgcn_cvt_pk_f32_fp8(vv[i][e], false);
-        vf[2 * e + 1] = __builtin_amdgcn_cvt_pk_f32_fp8(vv[i][e], true);
+        const f32x4_t f = fp8x4_f32(vv[i][e]);
+        vf[2 * e] = f.lo;
+        vf[2 * e + 1] = f.hi;
       }
 #pragma unroll
       for (int g = 0; g < G; ++g) {

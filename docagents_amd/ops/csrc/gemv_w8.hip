@@ -8,13 +8,14 @@
 //    non-temporal): a k-block is 1024 e4m3 elements, so K % 1024 == 0;
 //  * R rows x U k-blocks of weight loads are issued before any FMA; the activation (two 16-B
 //    loads per lane per k-block) and the gain vector go through the caches;
-//  * v_cvt_pk_f32_fp8 unpacks two weights per instruction (8 per 16-B load), fp32 accumulators
+//  * v_cvt_pk_f32_fp8 (fp8x4_f32, fp8.h) unpacks two weights per instruction, fp32 accumulators
 //    per lane, one wave reduction per row; the row scale and the RMSNorm factor are applied after
 //    the reduction, in fp32;
 //  * KS = 2: two neighbouring waves of a workgroup split a row's K range and combine their partial
 //    sums (and sums of squares) through LDS — long rows on narrow matrices (K = 8192 down projection);
 //  * EPI_SWIGLU: a wave owns 2 gate rows and their 2 up rows (16-row interleave) -> 2 outputs; the
 //    row scales apply before silu.
+#include "fp8.h"
 #include "gemm.h"
 
 struct GemvW8Args {
@@ -101,12 +102,9 @@ gemv_w8_kernel(GemvW8Args p) {
       for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {  // word e = weights 4e .. 4e+3 of this lane's 16
-          const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(wq[u][r][e], false);
-          const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(wq[u][r][e], true);
-          acc[r] = fmaf(lo[0], a[4 * e], acc[r]);
-          acc[r] = fmaf(lo[1], a[4 * e + 1], acc[r]);
-          acc[r] = fmaf(hi[0], a[4 * e + 2], acc[r]);
-          acc[r] = fmaf(hi[1], a[4 * e + 3], acc[r]);
+          const f32x4_t wf = fp8x4_f32(wq[u][r][e]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[r] = fmaf(wf[j], a[4 * e + j], acc[r]);
         }
     }
   }

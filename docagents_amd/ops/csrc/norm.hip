@@ -5,6 +5,7 @@
 // Reference compute sites replaced: N1 (encoder LayerNorm / embeddings),
 // N3 (`normalize`, internal/embeddings/openai.go:146-158 -> fused pooling + L2 norm), N6 (RMSNorm).
 #include "common.h"
+#include "fp8.h"
 
 #define MAXCH 8  // max 8-element chunks per thread (D <= 8 * 8 * 256 = 16384)
 
@@ -131,11 +132,7 @@ __device__ __forceinline__ void store_row_fp8(float (&v)[MAXCH][8], int nch, int
   for (int i = 0; i < MAXCH; ++i) {
     const int c = threadIdx.x + i * blockDim.x;
     if (c < nch) {
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][4] * inv, v[i][5] * inv, 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][6] * inv, v[i][7] * inv, hi, true);
-      *(u32x2_t*)(yq + (size_t)row * ldq + c * 8) = u32x2_t{(unsigned)lo, (unsigned)hi};
+      *(u32x2_t*)(yq + (size_t)row * ldq + c * 8) = f32x8_fp8(v[i], inv);
     }
   }
 }
@@ -350,11 +347,7 @@ __global__ void quant_fp8_rows_kernel(const bf16_t* __restrict__ x, int ldx, int
   for (int i = 0; i < MAXCH; ++i) {
     const int c = threadIdx.x + i * blockDim.x;
     if (c < nch) {
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][4] * inv, v[i][5] * inv, 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][6] * inv, v[i][7] * inv, hi, true);
-      *(u32x2_t*)(out + (size_t)row * ldo + c * 8) = u32x2_t{(unsigned)lo, (unsigned)hi};
+      *(u32x2_t*)(out + (size_t)row * ldo + c * 8) = f32x8_fp8(v[i], inv);
     }
   }
 }

@@ -2,29 +2,21 @@
 // vecsearch.hip (INDEX_DTYPE=fp8).
 //
 // Storage: a row of d values is d e4m3 codes plus ONE fp32 power-of-two scale: the smallest 2^e with
-// amax / 2^e <= 448 (1 for an all-zero row), the rule of the fp8 KV cache and of
-// quant_weight_fp8_pow2. code * 2^e is exact in bf16.
+// amax / 2^e <= 448 (1 for an all-zero row): fp8_pow2_scale (fp8.h). code * 2^e is exact in bf16.
 //   codes [N, d]  one byte each        scale [N] fp32
 // A scan streams d + 4 bytes per row instead of 2 d. Queries stay bf16 and the MFMA stays bf16: the
-// codes are unpacked in registers (v_cvt_pk_f32_fp8, then packed to bf16 — exact), so a score is
+// codes are unpacked in registers (cvt8_bf16, fp8.h — exact), so a score is
 // scale[row] * sum(code_i * q_i) with fp32 accumulation: the search of the bf16 matrix codes * scale,
 // up to fp32 summation order. Candidate lists (TdWave) and the final merge are the bf16 scans'.
+#include "fp8.h"
 #include "vecsearch_topk.h"
 
 extern "C" int da_topk_merge(void* cand_s, void* cand_i, int P, int Q, int K, void* out_s, void* out_i, void* stream);
 
-// 8 codes (two dwords, memory order) -> one MFMA A fragment of 8 bf16
-__device__ __forceinline__ bf16x8_t cvt8_bf16(unsigned w0, unsigned w1) {
-  const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(w0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(w0, true);
-  const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8(w1, false), e = __builtin_amdgcn_cvt_pk_f32_fp8(w1, true);
-  const u32x4_t r = {pack_bf2(a[0], a[1]), pack_bf2(b[0], b[1]), pack_bf2(c[0], c[1]), pack_bf2(e[0], e[1])};
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
 // ------------------------------------------------------------------------------------------------
 // bf16 rows X [n, d] -> codes[(row0 + r) * d ..] and scale[row0 + r]. One wave per row (4 elements
-// per lane per step of 256), amax over the row by lane shuffles; the exponent arithmetic of
-// rope_cache_kv8_kernel. Writes nothing outside rows [row0, row0 + n).
+// per lane per step of 256), amax over the row by lane shuffles, then fp8_pow2_scale. Writes nothing
+// outside rows [row0, row0 + n).
 __global__ void __launch_bounds__(256)
 index_quant_rows_kernel(const bf16_t* __restrict__ X, int n, int d, uint8_t* __restrict__ codes,
                         float* __restrict__ scale, long long row0) {
@@ -39,18 +31,12 @@ index_quant_rows_kernel(const bf16_t* __restrict__ X, int n, int d, uint8_t* __r
                  fmaxf(fabsf(bf2f(a[1] & 0xffff)), fabsf(bf2f(a[1] >> 16))));
   }
   amax = wave_max(amax);
-  // smallest 2^e with amax / 2^e <= 448 = 1.75 * 2^8: amax = f * 2^E, f in [1, 2) -> e = E - 8 (+ 1 if f > 1.75)
-  const unsigned ab = __float_as_uint(amax);
-  int e = (int)(ab >> 23) - 127 - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
-  e = max(e, -126);
-  if (amax == 0.f) e = 0;
-  const float sc = __uint_as_float((unsigned)(127 + e) << 23), inv = __uint_as_float((unsigned)(127 - e) << 23);
+  float sc, inv;
+  fp8_pow2_scale(amax, sc, inv);
   uint8_t* cr = codes + ((size_t)row0 + r) * d;
   for (int j = lane * 4; j < d; j += 256) {
     const u32x2_t a = *(const u32x2_t*)(xr + j);
-    int code = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(a[0] & 0xffff) * inv, bf2f(a[0] >> 16) * inv, 0, false);
-    code = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(a[1] & 0xffff) * inv, bf2f(a[1] >> 16) * inv, code, true);
-    *(int*)(cr + j) = code;
+    *(unsigned*)(cr + j) = f32x4_fp8(bf2f(a[0] & 0xffff), bf2f(a[0] >> 16), bf2f(a[1] & 0xffff), bf2f(a[1] >> 16), inv);
   }
   if (lane == 0) scale[row0 + r] = sc;
 }
@@ -345,12 +331,9 @@ topk_ranges8_kernel(const uint8_t* __restrict__ C, const float* __restrict__ sca
               const u32x4_t u = *(const u32x4_t*)(cr + c * 16);
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(u[e], false);
-                const f32x2_t b = __builtin_amdgcn_cvt_pk_f32_fp8(u[e], true);
-                dot += qv[i][4 * e] * a[0];
-                dot += qv[i][4 * e + 1] * a[1];
-                dot += qv[i][4 * e + 2] * b[0];
-                dot += qv[i][4 * e + 3] * b[1];
+                const f32x4_t f = fp8x4_f32(u[e]);
+#pragma unroll
+                for (int x = 0; x < 4; ++x) dot += qv[i][4 * e + x] * f[x];
               }
             }
           }

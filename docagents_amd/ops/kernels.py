@@ -20,6 +20,7 @@ import torch
 from . import gemm_plan
 from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: F401 - re-exported
                         gemv_fusable, gemv_w8_fusable)
+from .reference import quant_weight_fp8, quant_weight_fp8_pow2  # noqa: F401 - host-side torch, done once at load
 
 _LIB = None
 _LOCK = threading.Lock()
@@ -291,33 +292,60 @@ def gemm_route(M: int, N: int, K: int, epi: int = EPI_NONE):
     return {"tile": p.tile, "splits": p.splits}
 
 
+def _dk_operands(name, a, N, max_m, epi, bias, resid, out, norm_in, ssq_out):
+    """The operand checks gemm_dk and gemm_dk_w8 share (everything but the weights; every pointer the
+    kernel body reads or writes 16 B at a time is 16-B aligned). Allocates ``out`` if None. Returns
+    (M, N, K, nout, out, ldr, ssq, parts, eps); raises ValueError before any launch."""
+    _bf16_cuda(a, "a")
+    _req(a.dim() == 2, f"{name} expects 2-D operands")
+    M, K = a.shape
+    _req(1 <= M <= max_m and K >= 256 and K % 256 == 0 and N >= 16 and N % 16 == 0, f"{name} shape M={M} N={N} K={K}")
+    _req(epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0),
+         f"{name} does not take epi={epi} at N={N}")
+    _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.stride(0) >= K and a.data_ptr() % 16 == 0,
+         "a must be row-major, 16-B aligned rows")
+    nout = N // 2 if epi == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
+    _bf16_cuda(out, "out")
+    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         "bad out")
+    if bias is not None:
+        _bf16_cuda(bias, "bias")
+        _req(bias.numel() == N and bias.is_contiguous() and bias.data_ptr() % 16 == 0, "bias must be [N]")
+        _req(epi in (EPI_BIAS, EPI_RESID), "bias only with BIAS/RESID epilogues")
+    ldr = 0
+    if epi == EPI_RESID:
+        _req(resid is not None, "EPI_RESID needs resid")
+        _bf16_cuda(resid, "resid")
+        _req(resid.shape == (M, N) and resid.stride(1) == 1 and resid.stride(0) % 8 == 0
+             and resid.data_ptr() % 16 == 0, "bad resid")
+        ldr = resid.stride(0)
+    ssq, parts, eps = (None, 0, 0.0) if norm_in is None else norm_in
+    if ssq is not None:
+        _req(epi != EPI_RESID, "a residual producer takes no deferred norm")
+        _req(ssq.is_cuda and ssq.dtype == torch.float32 and ssq.is_contiguous() and parts >= 1
+             and ssq.numel() >= parts * 64 and ssq.data_ptr() % 16 == 0 and eps > 0, "bad ssq_in")
+    if ssq_out is not None:
+        _req(epi == EPI_RESID, "ssq_out needs the residual epilogue")
+        _req(ssq_out.is_cuda and ssq_out.dtype == torch.float32 and ssq_out.is_contiguous()
+             and ssq_out.numel() >= dk_parts(N, M) * 64, "bad ssq_out")
+    return M, N, K, nout, out, ldr, ssq, parts, eps
+
+
 def gemm_dk(a, w, epi: int = EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
     """Decode-sized product (1 <= M <= 64) in one launch without split-K:
     out = epi(rownorm(a) @ w^T). norm_in = (ssq, parts, eps): ``a`` is the raw residual stream and
     each row is scaled by rsqrt(sum of ssq[:parts, row] / K + eps) first (bf16-rounded, as the
     rmsnorm kernel would; RMSNorm gains folded into w). ssq_out (EPI_RESID only): fp32
     [dk_parts(N), 64] receives the per-part sums of squares of the new rows, for the next consumer."""
-    _bf16_cuda(a, "a"); _bf16_cuda(w, "w")
-    M, K = a.shape
-    N = w.shape[0]
-    _req(1 <= M <= 64 and K % 256 == 0 and N % 16 == 0 and w.shape[1] == K, f"gemm_dk shape M={M} N={N} K={K}")
-    _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and w.is_contiguous(), "gemm_dk layout")
-    _req(a.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0, "operands must be 16-B aligned")
-    nout = N // 2 if epi == EPI_SWIGLU else N
-    if out is None:
-        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
-    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0, "bad out")
-    ldr = 0
-    if epi == EPI_RESID:
-        _req(resid is not None and resid.shape == (M, N) and resid.stride(1) == 1 and resid.stride(0) % 8 == 0,
-             "bad resid")
-        ldr = resid.stride(0)
-    ssq, parts, eps = (None, 0, 0.0) if norm_in is None else norm_in
-    if ssq is not None:
-        _req(ssq.dtype == torch.float32 and ssq.is_contiguous() and ssq.numel() >= parts * 64, "bad ssq_in")
-    if ssq_out is not None:
-        _req(epi == EPI_RESID and ssq_out.dtype == torch.float32 and ssq_out.is_contiguous()
-             and ssq_out.numel() >= dk_parts(N, M) * 64, "bad ssq_out")
+    _bf16_cuda(w, "w")
+    _req(w.dim() == 2 and w.is_contiguous() and w.data_ptr() % 16 == 0, "w must be contiguous, 16-B aligned")
+    M, N, K, _, out, ldr, ssq, parts, eps = _dk_operands("gemm_dk", a, w.shape[0], DK_MAX_M, epi, bias, resid, out,
+                                                         norm_in, ssq_out)
+    _req(w.shape[1] == K, f"K mismatch {K} vs {w.shape[1]}")
+    if epi != EPI_RESID:
+        resid = None
     p = gemm_plan.plan_dk(M, N, K, ssq_out is not None)
     if p.family == "dk_splitk":
         ws = _workspace(p.ws_bytes, a.device)
@@ -383,27 +411,6 @@ def quant_fp8(x: torch.Tensor, out=None, scale=None):
     return out, scale
 
 
-def quant_weight_fp8(w: torch.Tensor):
-    """Per-output-channel e4m3 weight quantisation (host-side torch; done once at load)."""
-    wf = w.float()
-    sw = (wf.abs().amax(dim=1) / 448.0).clamp_min(1e-30)
-    return (wf / sw[:, None]).clamp(-448, 448).to(FP8).contiguous(), sw.contiguous()
-
-
-def quant_weight_fp8_pow2(w: torch.Tensor):
-    """Per-output-row e4m3 quantisation with a power-of-two row scale (host-side torch; done once at
-    load): s = the smallest 2^e with amax_row / 2^e <= 448 (all-zero rows: 1). An e4m3 value times a
-    power of two is exact in bf16, so ``q.float() * s[:, None]`` IS a bf16 matrix: the bf16 kernels
-    and the fp8 GEMV compute the same model. Returns (q [N, K] float8_e4m3fn, s [N] fp32)."""
-    wf = w.float()
-    amax = wf.abs().amax(dim=1)
-    s = torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -100) / 448.0)))
-    s = torch.where(amax / s > 448.0, s * 2, s)        # log2 rounding at an exact power-of-two ratio
-    s = torch.where(amax / (s / 2) <= 448.0, s / 2, s)
-    s = torch.where(amax > 0, s, torch.ones_like(s))
-    return (wf / s[:, None]).clamp(-448, 448).to(FP8).contiguous(), s.contiguous()
-
-
 def gemm_w8(a: torch.Tensor, wq: torch.Tensor, sw: torch.Tensor, bias=None, epi: int = EPI_NONE, resid=None,
             out=None, rms=None) -> torch.Tensor:
     """out[1, N'] = epi((a[1, K] @ wq[N, K]^T) * sw[None, :]) with e4m3 weights and fp32 row scales
@@ -450,49 +457,15 @@ def gemm_dk_w8(a, wq, sw, epi: int = EPI_NONE, bias=None, resid=None, out=None, 
     """gemm_dk on e4m3 weights with fp32 row scales (1 <= M <= 32), one launch:
     out = epi((rownorm(a) @ wq^T) * sw[None, :]). norm_in / ssq_out as gemm_dk (dk_parts(N, M) parts: a residual
     producer tiles like gemm_dk's). Anything the kernel would refuse raises ValueError before any launch."""
-    _bf16_cuda(a, "a")
     _req(wq.is_cuda and wq.dtype == FP8, f"wq must be float8_e4m3fn on GPU, got {wq.dtype}")
-    _req(a.dim() == 2 and wq.dim() == 2, "gemm_dk_w8 expects 2-D operands")
-    M, K = a.shape
-    N, K2 = wq.shape
-    _req(K == K2, f"K mismatch {K} vs {K2}")
-    _req(1 <= M <= gemm_plan.DK_W8_MAX_M and K >= 256 and K % 256 == 0 and N >= 16 and N % 16 == 0,
-         f"gemm_dk_w8 shape M={M} N={N} K={K}")
-    _req(epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0),
-         f"gemm_dk_w8 does not take epi={epi} at N={N}")
-    _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.stride(0) >= K, "a must be row-major, 16-B aligned rows")
-    _req(wq.is_contiguous(), "wq must be contiguous")
-    _req(sw.is_cuda and sw.dtype == torch.float32 and sw.is_contiguous() and sw.shape == (N,), "sw must be fp32 [N]")
-    _req(a.data_ptr() % 16 == 0 and wq.data_ptr() % 16 == 0 and sw.data_ptr() % 16 == 0,
-         "operands must be 16-B aligned")
-    nout = N // 2 if epi == EPI_SWIGLU else N
-    if out is None:
-        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
-    _bf16_cuda(out, "out")
-    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
-         "bad out")
-    if bias is not None:
-        _bf16_cuda(bias, "bias")
-        _req(bias.numel() == N and bias.is_contiguous() and bias.data_ptr() % 16 == 0, "bias must be [N]")
-        _req(epi in (EPI_BIAS, EPI_RESID), "bias only with BIAS/RESID epilogues")
-    ldr = 0
-    if epi == EPI_RESID:
-        _req(resid is not None, "EPI_RESID needs resid")
-        _bf16_cuda(resid, "resid")
-        _req(resid.shape == (M, N) and resid.stride(1) == 1 and resid.stride(0) % 8 == 0
-             and resid.data_ptr() % 16 == 0, "bad resid")
-        ldr = resid.stride(0)
-    else:
+    _req(wq.dim() == 2 and wq.is_contiguous() and wq.data_ptr() % 16 == 0, "wq must be contiguous, 16-B aligned")
+    M, N, K, _, out, ldr, ssq, parts, eps = _dk_operands("gemm_dk_w8", a, wq.shape[0], gemm_plan.DK_W8_MAX_M, epi,
+                                                         bias, resid, out, norm_in, ssq_out)
+    _req(wq.shape[1] == K, f"K mismatch {K} vs {wq.shape[1]}")
+    _req(sw.is_cuda and sw.dtype == torch.float32 and sw.is_contiguous() and sw.shape == (N,)
+         and sw.data_ptr() % 16 == 0, "sw must be fp32 [N], 16-B aligned")
+    if epi != EPI_RESID:
         resid = None
-    ssq, parts, eps = (None, 0, 0.0) if norm_in is None else norm_in
-    if ssq is not None:
-        _req(epi != EPI_RESID, "a residual producer takes no deferred norm")
-        _req(ssq.is_cuda and ssq.dtype == torch.float32 and ssq.is_contiguous() and parts >= 1
-             and ssq.numel() >= parts * 64 and ssq.data_ptr() % 16 == 0 and eps > 0, "bad ssq_in")
-    if ssq_out is not None:
-        _req(epi == EPI_RESID, "ssq_out needs the residual epilogue")
-        _req(ssq_out.is_cuda and ssq_out.dtype == torch.float32 and ssq_out.is_contiguous()
-             and ssq_out.numel() >= dk_parts(N, M) * 64, "bad ssq_out")
     _check(lib().da_gemm_dk_w8(_ptr(a), a.stride(0), _ptr(wq), _ptr(sw), _ptr(out), out.stride(0), _ptr(bias),
                                _ptr(resid), ldr, M, N, K, epi, _ptr(ssq), parts, K, float(eps), _ptr(ssq_out),
                                _stream()), "gemm_dk_w8")

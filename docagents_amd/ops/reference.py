@@ -478,17 +478,21 @@ def gemm_fp8(aq, sa, wq, sw, bias=None, epi=EPI_NONE, resid=None, out=None):
 
 
 def quant_weight_fp8(w):
+    """Per-output-channel e4m3 weight quantisation (host-side torch; done once at load)."""
     wf = w.float()
     sw = (wf.abs().amax(dim=1) / 448.0).clamp_min(1e-30)
     return (wf / sw[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), sw.contiguous()
 
 
 def quant_weight_fp8_pow2(w):
-    """kernels.quant_weight_fp8_pow2: e4m3 rows with the smallest power-of-two scale that fits 448."""
+    """Per-output-row e4m3 quantisation with a power-of-two row scale (host-side torch; done once at
+    load): s = the smallest 2^e with amax_row / 2^e <= 448 (all-zero rows: 1). An e4m3 value times a
+    power of two is exact in bf16, so ``q.float() * s[:, None]`` IS a bf16 matrix: the bf16 kernels
+    and the fp8 kernels compute the same model. Returns (q [N, K] float8_e4m3fn, s [N] fp32)."""
     wf = w.float()
     amax = wf.abs().amax(dim=1)
     s = torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -100) / 448.0)))
-    s = torch.where(amax / s > 448.0, s * 2, s)
+    s = torch.where(amax / s > 448.0, s * 2, s)        # log2 rounding at an exact power-of-two ratio
     s = torch.where(amax / (s / 2) <= 448.0, s / 2, s)
     s = torch.where(amax > 0, s, torch.ones_like(s))
     return (wf / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), s.contiguous()

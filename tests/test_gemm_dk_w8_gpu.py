@@ -15,9 +15,14 @@ DEV = "cuda"
 # one k-chunk (shorter than the prefetch ring), BN 16; SwiGLU BN 32; SwiGLU BN 64 with a ragged last
 # tile (12320 % 64 == 32); BN 16 long rows; BN 64 at 144 tiles (the fp8 rule; gemm_dk: BN 32); BN 16 at
 # K = 8192; BN 64 with a ragged last tile; and, beyond the issue's list, BN 32 without SwiGLU with a
-# ragged last tile (6160 = 192 x 32 + 16)
+# ragged last tile (6160 = 192 x 32 + 16). Then the edges of the body the two kernels share: one tile
+# and three tiles of 16 / of 32 (SwiGLU) at K = 768 (three chunks: no multiple of either prefetch depth)
+# and K = 2048, the ragged 64-wide SwiGLU tile at one chunk, and a ragged 64-wide tile by the fp8 rule
+# alone (9248 = 144 x 64 + 32)
 PRODUCTS = [(512, 256, K.EPI_BIAS), (1024, 512, K.EPI_SWIGLU), (12320, 512, K.EPI_SWIGLU), (3072, 3072, K.EPI_RESID),
-            (9216, 3072, K.EPI_NONE), (3072, 8192, K.EPI_RESID), (32064, 3072, K.EPI_NONE), (6160, 512, K.EPI_NONE)]
+            (9216, 3072, K.EPI_NONE), (3072, 8192, K.EPI_RESID), (32064, 3072, K.EPI_NONE), (6160, 512, K.EPI_NONE),
+            (16, 768, K.EPI_NONE), (48, 2048, K.EPI_RESID), (32, 768, K.EPI_SWIGLU), (96, 2048, K.EPI_SWIGLU),
+            (12320, 256, K.EPI_SWIGLU), (9248, 768, K.EPI_NONE)]
 ROWS = [2, 16, 17, 32]
 
 
@@ -72,7 +77,7 @@ def test_gemm_dk_w8_equals_bf16_gemm_dk_on_dequantised_weights(M, N, Kd, epi):
 
 
 @pytest.mark.parametrize("M", [3, 16, 32])
-@pytest.mark.parametrize("H,F", [(1024, 1024), (3072, 8192)])
+@pytest.mark.parametrize("H,F", [(1024, 1024), (3072, 8192), (768, 1024), (2048, 1024)])
 def test_gemm_dk_w8_deferred_norm_chain(M, H, F):
     """Producer (EPI_RESID + per-part sums of squares) -> consumer (deferred RMSNorm of its A rows)
     == residual add, rmsnorm kernel, reference GEMM; the sums match the fp32 row sums

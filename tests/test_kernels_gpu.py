@@ -878,11 +878,13 @@ def test_gemm_dk_matches_reference(M, N, Kd, epi):
         assert torch.equal(K.gemm(a, w, epi=epi, resid=r, bias=bias), got)
 
 
-@pytest.mark.parametrize("M", [3, 16, 40, 64])
-@pytest.mark.parametrize("H,F", [(3072, 8192), (4096, 14336)])
+@pytest.mark.parametrize("H,F,M", [(H, F, M) for H, F in [(3072, 8192), (4096, 14336)] for M in [3, 16, 40, 64]]
+                         + [(H, 1024, M) for H in (768, 2304) for M in (33, 64)])
 def test_gemm_dk_deferred_norm_chain(M, H, F):
     """Producer (EPI_RESID + per-part sums of squares) -> consumer (deferred RMSNorm of its A rows)
-    == residual add, rmsnorm kernel, plain GEMM; the sums match the fp32 row sums."""
+    == residual add, rmsnorm kernel, plain GEMM; the sums match the fp32 row sums. H = 768 / 2304 at
+    33 / 64 rows: H % 512 != 0, so the producer is gemm_dk_kernel's two row blocks (the second block
+    one row / full) over 3 / 9 k-chunks, one part per 16-wide tile."""
     torch.manual_seed(M + H)
     a, wo = _rand(M, H), _rand(H, H, scale=H ** -0.5)
     x = _rand(M, H)
