@@ -115,7 +115,7 @@ DA_EXPORT int da_kv8_dequant(const void* codes, const void* scale, int slot, int
 
 // ------------------------------------------------------------------------------------------
 // Split-KV decode attention over the fp8 cache: the structure of decode_attn_kernel<D, G, 3>
-// (attention.hip; the streaming form the batch-128 step runs) at half the bytes per key.
+// (decode_attn.hip; the streaming form the batch-128 step runs) at half the bytes per key.
 //   grid (nsplit, Hkv, B), 4 waves; each wave streams its own 64-key tiles with its own online
 //   softmax (no block barrier in the loop); the waves merge once at the end, the splits through
 //   dec_store / dec_finish (or decode_combine_kernel).
@@ -372,14 +372,15 @@ decode_attn_kv8_kernel(const bf16_t* __restrict__ q, int ldq, const uint8_t* __r
   dec_finish<D, G>(po, pm, pl, H, Hkv, nsplit, b, hk, cnt, out, ldo, &s_last);
 }
 
+struct DecKv8Args : DecArgs {
+  const uint8_t* kc; const uint8_t* vc;  // codes
+  const float* ksc; const float* vsc;    // row scales
+};
+
 template <int D>
-static int launch_decode_kv8(int G, dim3 grid, hipStream_t s, const bf16_t* q, int ldq, const uint8_t* kc,
-                             const uint8_t* vc, const float* ksc, const float* vsc, const int* lens, const int* slot,
-                             const int* pre, int H, int Hkv, int max_seq, int chunk, int nsplit, float sl2e, float* po,
-                             float* pm, float* pl, bf16_t* out, int ldo, int* cnt) {
-#define DEC8(GG) decode_attn_kv8_kernel<D, GG><<<grid, 256, 0, s>>>(q, ldq, kc, vc, ksc, vsc, lens, slot, pre, H, Hkv, \
-                                                                     max_seq, chunk, nsplit, sl2e, po, pm, pl, out, ldo, cnt)
-  switch (G) {
+static int launch_decode_kv8(const DecKv8Args& a) {
+#define DEC8(GG) decode_attn_kv8_kernel<D, GG><<<a.grid, 256, 0, a.s>>>(a.q, a.ldq, a.kc, a.vc, a.ksc, a.vsc, DEC_KARGS(a))
+  switch (a.G) {
     case 1: DEC8(1); break;
     case 2: DEC8(2); break;
     case 4: DEC8(4); break;
@@ -397,37 +398,13 @@ DA_EXPORT int da_decode_attn_kv8(const void* q, int ldq, const void* k_codes, co
                                  const void* k_scale, const void* v_scale, const void* lens, const void* slot,
                                  const void* pre, int B, int H, int Hkv, int D, int max_seq, int chunk, int nsplit,
                                  float scale, void* ws, void* o, int ldo, void* counters, void* stream) {
-  if (Hkv < 1 || H % Hkv || chunk < 64 || chunk % 64 || nsplit < 1) return (int)hipErrorInvalidValue;
-  if (!q || !k_codes || !v_codes || !k_scale || !v_scale || !lens || !slot || !o || (nsplit > 1 && !ws))
+  DecKv8Args a;
+  if (dec_fill(a, q, ldq, lens, slot, pre, B, H, Hkv, D, max_seq, chunk, nsplit, scale, ws, o, ldo, counters, nullptr,
+               nullptr, stream) || !k_codes || !v_codes || !k_scale || !v_scale)
     return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
-  const int G = H / Hkv;
-  float* po = (float*)ws;
-  float* pm = po + (size_t)B * H * nsplit * D;
-  float* pl = pm + (size_t)B * H * nsplit;
-  int* cnt = (int*)counters;
-  bf16_t* out = (bf16_t*)o;
-  dim3 grid(nsplit, Hkv, B);
-  const float sl2e = scale * 1.4426950408889634f;
-  hipStream_t s = (hipStream_t)stream;
-#define KV8_ARGS G, grid, s, (const bf16_t*)q, ldq, (const uint8_t*)k_codes, (const uint8_t*)v_codes, \
-                 (const float*)k_scale, (const float*)v_scale, (const int*)lens, (const int*)slot, (const int*)pre, H, \
-                 Hkv, max_seq, chunk, nsplit, sl2e, po, pm, pl, out, ldo, cnt
-  int err;
-  switch (D) {
-    case 64: err = launch_decode_kv8<64>(KV8_ARGS); break;
-    case 96: err = launch_decode_kv8<96>(KV8_ARGS); break;
-    case 128: err = launch_decode_kv8<128>(KV8_ARGS); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef KV8_ARGS
-  if (err) return err;
-  if (nsplit == 1 || cnt) return 0;
-  dim3 cgrid(H, B);
-  switch (D) {
-    case 64: decode_combine_kernel<64><<<cgrid, 64, 0, s>>>(po, pm, pl, H, nsplit, out, ldo); break;
-    case 96: decode_combine_kernel<96><<<cgrid, 128, 0, s>>>(po, pm, pl, H, nsplit, out, ldo); break;
-    case 128: decode_combine_kernel<128><<<cgrid, 128, 0, s>>>(po, pm, pl, H, nsplit, out, ldo); break;
-  }
-  DA_LAUNCH_CHECK();
+  a.kc = (const uint8_t*)k_codes; a.vc = (const uint8_t*)v_codes;
+  a.ksc = (const float*)k_scale; a.vsc = (const float*)v_scale;
+  const int err = D == 64 ? launch_decode_kv8<64>(a) : D == 96 ? launch_decode_kv8<96>(a) : launch_decode_kv8<128>(a);
+  return err ? err : dec_combine(a);
 }

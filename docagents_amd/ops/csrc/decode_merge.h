@@ -1,6 +1,7 @@
-// Split-KV merge machinery shared by the decode-attention kernels (attention.hip: bf16 cache;
-// decode_kv8.hip: fp8 cache): keys per split, the per-split store, the in-kernel merge by the last
-// split of a (row, kv head) pair, and the separate combine kernel.
+// What the decode-attention kernels share (decode_attn.hip: bf16 cache; decode_kv8.hip: fp8 cache).
+// Device side, the split-KV merge machinery: keys per split, the per-split store, the in-kernel merge
+// by the last split of a (row, kv head) pair, and the separate combine kernel. Host side (at the end):
+// the launch arguments (DecArgs), their checks (dec_fill) and the combine launch (dec_combine).
 #pragma once
 #include "common.h"
 
@@ -115,4 +116,56 @@ __global__ void decode_combine_kernel(const float* __restrict__ po, const float*
     for (int s = 0; s < nsplit; ++s) acc += po[(base + s) * D + d] * exp2f(pm[base + s] - Mu);
     o[(size_t)b * ldo + h * D + d] = f2bf(acc * inv);
   }
+}
+
+// ---- host: one launch's arguments, cache operands excepted (each file derives its own struct) ----
+struct DecArgs {
+  const bf16_t* q; const int* lens; const int* slot; const int* pre;
+  int ldq, B, H, Hkv, G, D, max_seq, chunk, nsplit, ldo;
+  float sl2e;                        // scale * log2(e)
+  float* po; float* pm; float* pl;   // split partials in ws: po [B, H, nsplit, D], pm / pl [B, H, nsplit]
+  bf16_t* out; int* cnt;
+  dim3 grid;                         // (nsplit, Hkv, B)
+  hipStream_t s;
+};
+// the decode kernels' parameters that follow (q, ldq, <cache operands>)
+#define DEC_KARGS(a) (a).lens, (a).slot, (a).pre, (a).H, (a).Hkv, (a).max_seq, (a).chunk, (a).nsplit, (a).sl2e, (a).po, \
+                     (a).pm, (a).pl, (a).out, (a).ldo, (a).cnt
+
+// Checks what every decode kernel relies on and fills the arguments; the cache pointers are the
+// caller's to check. 0, or hipErrorInvalidValue: refused. B == 0 passes (nothing to launch).
+// ws must hold B*H*nsplit*(D+2) floats. chunk = keys per split (multiple of 64).
+// pre (nullable): int32 [B][2] = (P, prefix slot) per row — keys [0, P) of row b are read from the
+// prefix slot (a prompt head shared by the whole batch, stored once; P % 64 == 0 so no 64-key tile
+// straddles the two sources). Every row of the batch reads the same prefix lines, so they are served
+// from L2 / MALL instead of HBM.
+// counters (nullable): int32 [B * Hkv], all zero, left zero by every launch -> the splits are merged
+// inside the attention kernel (last split per (b, kv head)); null -> separate combine launch. With
+// counters, ws and counters must be uncached allocations (da_malloc_uncached).
+// cos_sin / pos (both null, or both set): fused RoPE + new-token KV-cache write (bf16 cache, MHA
+// only; q is then the raw qkv row, see DecRope).
+static inline int dec_fill(DecArgs& a, const void* q, int ldq, const void* lens, const void* slot, const void* pre,
+                           int B, int H, int Hkv, int D, int max_seq, int chunk, int nsplit, float scale, void* ws,
+                           void* o, int ldo, void* counters, const void* cos_sin, const void* pos, void* stream) {
+  bool ok = Hkv >= 1 && H % Hkv == 0 && chunk >= 64 && chunk % 64 == 0 && nsplit >= 1 && (D == 64 || D == 96 || D == 128);
+  ok = ok && q && lens && slot && o && (nsplit == 1 || ws);
+  ok = ok && (cos_sin == nullptr) == (pos == nullptr) && (!cos_sin || (H == Hkv && ldq >= (H + 2 * Hkv) * D));
+  if (!ok) return (int)hipErrorInvalidValue;
+  a.q = (const bf16_t*)q; a.lens = (const int*)lens; a.slot = (const int*)slot; a.pre = (const int*)pre;
+  a.ldq = ldq; a.B = B; a.H = H; a.Hkv = Hkv; a.G = H / Hkv; a.D = D; a.max_seq = max_seq; a.chunk = chunk;
+  a.nsplit = nsplit; a.ldo = ldo;
+  a.sl2e = scale * 1.4426950408889634f;
+  a.po = (float*)ws; a.pm = a.po + (size_t)B * H * nsplit * D; a.pl = a.pm + (size_t)B * H * nsplit;
+  a.out = (bf16_t*)o; a.cnt = (int*)counters;
+  a.grid = dim3(nsplit, Hkv, B); a.s = (hipStream_t)stream;
+  return 0;
+}
+
+// The separate merge of the splits, when the kernel did not do it (no counters).
+static inline int dec_combine(const DecArgs& a) {
+  if (a.nsplit == 1 || a.cnt) return 0;
+#define DEC_COMBINE(DD, NT) decode_combine_kernel<DD><<<dim3(a.H, a.B), NT, 0, a.s>>>(a.po, a.pm, a.pl, a.H, a.nsplit, a.out, a.ldo)
+  if (a.D == 64) DEC_COMBINE(64, 64); else if (a.D == 96) DEC_COMBINE(96, 128); else DEC_COMBINE(128, 128);
+#undef DEC_COMBINE
+  DA_LAUNCH_CHECK();
 }

@@ -720,7 +720,7 @@ def _decode_split(B: int, Hkv: int, max_len: int, chunk: int):
     return chunk, max(1, math.ceil(max_len / chunk))
 
 
-# Same-XCD split exchange of the batch-1..small-batch MHA decode attention (attention.hip, VAR bit 3):
+# Same-XCD split exchange of the batch-1..small-batch MHA decode attention (decode_attn.hip, DEC_XC):
 # all splits of a (row, kv head) pair on one XCD, their partials and ticket in cached memory (L2
 # round trips instead of uncached ones). It relies on the launch's workgroup -> XCD round-robin, so
 # it is used only after the placement probe confirmed that on this device, and never once a
@@ -764,13 +764,16 @@ def _cached_counters(tag: str, n: int, device) -> torch.Tensor:
     return bufs[-1]
 
 
-def _decode_checks(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len, pre, rope):
+def _decode_operands(q, lens, slot, H, Hkv, D, max_len, max_seq, chunk, out, pre, rope=None):
+    """The operand checks of both decode wrappers (the cache's own are the caller's; max_seq = its
+    capacity). Returns (chunk, nsplit, out, cos_sin, pos)."""
     _bf16_cuda(q, "q"); _i32(lens, "lens"); _i32(slot, "slot")
     _req(D in (64, 96, 128), "head dim")
-    _req((H // Hkv) in (1, 2, 4, 8) and H % Hkv == 0, "GQA group must be 1/2/4/8")
+    _req(H % Hkv == 0 and (H // Hkv) in (1, 2, 4, 8), "GQA group must be 1/2/4/8")
+    _req(q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= H * D, "q [B, >= H*D]")
     B = q.shape[0]
-    _req(k_cache.dim() == 4 and k_cache.shape[1] == Hkv and k_cache.shape[3] == D, "cache shape")
-    _req(max_len <= k_cache.shape[2], "max_len > cache capacity")
+    _req(lens.numel() >= B and slot.numel() >= B, "lens / slot length")
+    _req(0 < max_len <= max_seq, "max_len > cache capacity")
     if pre is not None:
         _i32(pre, "pre"); _req(pre.shape == (B, 2) and pre.is_contiguous(), "pre must be int32 [B, 2]")
     cs = ps = None
@@ -779,9 +782,28 @@ def _decode_checks(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len, pre, rop
         _req(H == Hkv and D % 8 == 0, "fused RoPE decode: MHA only")
         _i32(ps, "pos")
         _req(cs.dtype == torch.float32 and cs.is_contiguous() and cs.shape[1] == D // 2 and cs.shape[2] == 2, "cos_sin")
-        _req(q.stride(1) == 1 and q.shape[1] >= (H + 2 * Hkv) * D, "fused RoPE decode needs the qkv row")
-        _req(k_cache.is_contiguous() and v_cache.is_contiguous(), "caches must be contiguous")
-    return cs, ps
+        _req(q.shape[1] >= (H + 2 * Hkv) * D, "fused RoPE decode needs the qkv row")
+    chunk, nsplit = _decode_split(B, Hkv, max_len, chunk)
+    _req(chunk % 64 == 0, "chunk must be a multiple of 64")
+    if out is None:
+        out = torch.empty((B, H * D), dtype=torch.bfloat16, device=q.device)
+    _bf16_cuda(out, "out")
+    _req(out.dim() == 2 and out.shape[0] == B and out.shape[1] >= H * D and out.stride(1) == 1, "out [B, >= H*D]")
+    return chunk, nsplit, out, cs, ps
+
+
+def _decode_buffers(B, H, Hkv, D, nsplit, device, same_xcd_ok: bool):
+    """(ws, cnt, xc) of a launch: the split partials and, when the kernel merges them itself, the
+    tickets — in uncached memory, or (xc = 1, bf16 cache only: same_xcd_ok) in cached memory with all
+    splits of a (row, kv head) pair on one XCD. No tickets: a combine launch merges."""
+    nws = B * H * nsplit * (D + 2) * 4
+    ws = _workspace(nws, device)
+    if not (_FUSED_COMBINE and nsplit > 1):
+        return ws, None, 0
+    if same_xcd_ok and H == Hkv and B * Hkv <= 32 and (B * Hkv) % 8 == 0 and decode_xc_ok(device):
+        return ws, _cached_counters("decode_cnt_xc", B * Hkv, device), 1  # the role workspace: cached memory
+    cnt = _uncached("decode_cnt", B * Hkv * 4, device)
+    return _uncached("decode_ws", nws, device), cnt, 0
 
 
 def decode_attn(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len: int, chunk: int = 0, scale=None, out=None,
@@ -794,22 +816,13 @@ def decode_attn(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len: int, chunk:
     rope = (cos_sin fp32 [max_pos, D/2, 2], pos int32 [B]), MHA only: q is the raw qkv row
     [B, (H + 2 Hkv) D]; the kernel applies RoPE to q and the new token's k and writes that token's
     k / v into the cache at pos (== lens - 1) — the decode step's rope_cache launch folded in."""
-    cs, ps = _decode_checks(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len, pre, rope)
-    chunk, nsplit = _decode_split(q.shape[0], Hkv, max_len, chunk)
+    _req(k_cache.dim() == 4 and k_cache.shape[1] == Hkv and k_cache.shape[3] == D, "cache shape")
+    _req(rope is None or (k_cache.is_contiguous() and v_cache.is_contiguous()), "caches must be contiguous")
+    chunk, nsplit, out, cs, ps = _decode_operands(q, lens, slot, H, Hkv, D, max_len, k_cache.shape[2], chunk, out, pre,
+                                                  rope)
     B = q.shape[0]
-    ws = _workspace(B * H * nsplit * (D + 2) * 4, q.device)
-    if out is None:
-        out = torch.empty((B, H * D), dtype=torch.bfloat16, device=q.device)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    cnt = None
-    xc = 0
-    if _FUSED_COMBINE and nsplit > 1:
-        if H == Hkv and B * Hkv <= 32 and (B * Hkv) % 8 == 0 and decode_xc_ok(q.device):
-            xc = 1  # same-XCD exchange: ws (the role workspace) and counters in cached memory
-            cnt = _cached_counters("decode_cnt_xc", B * Hkv, q.device)
-        else:
-            cnt = _uncached("decode_cnt", B * Hkv * 4, q.device)
-            ws = _uncached("decode_ws", B * H * nsplit * (D + 2) * 4, q.device)
+    ws, cnt, xc = _decode_buffers(B, H, Hkv, D, nsplit, q.device, same_xcd_ok=True)
     _check(lib().da_decode_attn(_ptr(q), q.stride(0), _ptr(k_cache), _ptr(v_cache), _ptr(lens), _ptr(slot), _ptr(pre), B, H,
                                 Hkv, D, k_cache.shape[2], chunk, nsplit, float(scale), _ptr(ws), _ptr(out), out.stride(0),
                                 _ptr(cnt), _ptr(cs), _ptr(ps), xc, _stream()), "decode_attn")
@@ -853,29 +866,11 @@ def decode_attn_kv8(q, k_codes, v_codes, k_scale, v_scale, lens, slot, H, Hkv, D
     int32 [B], max_len fixes the split count (graph-capturable), pre int32 [B, 2] = (P, prefix slot)
     with P % 64 == 0, out bf16 with any row stride. Splits merge in the kernel through the uncached
     workspace and ticket (or a combine launch with _FUSED_COMBINE off); never the same-XCD exchange."""
-    _bf16_cuda(q, "q"); _i32(lens, "lens"); _i32(slot, "slot")
-    _req(D in (64, 96, 128), "head dim")
-    _req(H % Hkv == 0 and (H // Hkv) in (1, 2, 4, 8), "GQA group must be 1/2/4/8")
-    _req(q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= H * D, "q [B, >= H*D]")
-    B = q.shape[0]
-    _req(lens.numel() >= B and slot.numel() >= B, "lens / slot length")
     _kv8_cache_checks(k_codes, v_codes, k_scale, v_scale, Hkv, D)
-    _req(0 < max_len <= k_codes.shape[2], "max_len > cache capacity")
-    if pre is not None:
-        _i32(pre, "pre"); _req(pre.shape == (B, 2) and pre.is_contiguous(), "pre must be int32 [B, 2]")
-    chunk, nsplit = _decode_split(B, Hkv, max_len, chunk)
-    _req(chunk % 64 == 0, "chunk must be a multiple of 64")
-    if out is None:
-        out = torch.empty((B, H * D), dtype=torch.bfloat16, device=q.device)
-    _bf16_cuda(out, "out")
-    _req(out.dim() == 2 and out.shape[0] == B and out.shape[1] >= H * D and out.stride(1) == 1, "out [B, >= H*D]")
+    chunk, nsplit, out, _, _ = _decode_operands(q, lens, slot, H, Hkv, D, max_len, k_codes.shape[2], chunk, out, pre)
+    B = q.shape[0]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    nws = B * H * nsplit * (D + 2) * 4
-    ws = _workspace(nws, q.device)
-    cnt = None
-    if _FUSED_COMBINE and nsplit > 1:
-        cnt = _uncached("decode_cnt", B * Hkv * 4, q.device)
-        ws = _uncached("decode_ws", nws, q.device)
+    ws, cnt, _ = _decode_buffers(B, H, Hkv, D, nsplit, q.device, same_xcd_ok=False)
     _check(lib().da_decode_attn_kv8(_ptr(q), q.stride(0), _ptr(k_codes), _ptr(v_codes), _ptr(k_scale), _ptr(v_scale),
                                     _ptr(lens), _ptr(slot), _ptr(pre), B, H, Hkv, D, k_codes.shape[2], chunk, nsplit,
                                     float(scale), _ptr(ws), _ptr(out), out.stride(0), _ptr(cnt), _stream()),

@@ -296,10 +296,15 @@ def test_flash_attn_spike(D):
 @pytest.mark.parametrize("D", [64, 96, 128])
 @pytest.mark.parametrize("lens,chunk", [([1000], 512), ([1], 256), ([513, 257, 64], 256), ([2944] * 5, 0),
                                         ([65, 1024, 700], 64), ([2935], 0), ([1000, 3], 768),
-                                        ([300] * 9 + [1, 2000], 0), ([4000, 64, 129] * 4, 512)])
+                                        ([300] * 9 + [1, 2000], 0), ([4000, 64, 129] * 4, 512),
+                                        ([1500, 3, 1000], 1024), ([1000, 3], 512)])
 def test_decode_attn_fused_rope(D, lens, chunk):
     """Decode attention with RoPE + the new token's cache write folded in == rope_cache + attention,
-    on the small-batch (prefetching, B * Hkv <= 32) and the streaming (larger batches) variants."""
+    on the small-batch (prefetching, B * Hkv <= 32) and the streaming (larger batches) variants.
+    H = 4, so by (B, chunk): B * H <= 32 and chunk <= 512 the MFMA kernel (B = 2: 8 pairs, with the
+    same-XCD exchange), chunk > 512 the prefetching VALU kernel (B = 2: same-XCD form; B = 3: 12 pairs,
+    the plain form), B >= 9 the streaming one. Both launches (with and without rope) take the same
+    route and each is compared with the fp32 reference."""
     torch.manual_seed(D + len(lens) + chunk)
     B = len(lens)
     H, slots, max_seq = 4, B + 2, 4096
@@ -313,6 +318,7 @@ def test_decode_attn_fused_rope(D, lens, chunk):
     kc0, vc0 = kc.clone(), vc.clone()
     K.rope_cache(qkv2, pos, cs, H, H, D, slot=slot, k_cache=kc2, v_cache=vc2)
     want = K.decode_attn(qkv2, kc2, vc2, L, slot, H, H, D, max_seq, chunk=chunk)
+    _close(want, R.decode_attn(qkv2, kc2, vc2, L, slot, H, H, D), atol=0.02)
     got = K.decode_attn(qkv, kc, vc, L, slot, H, H, D, max_seq, chunk=chunk, rope=(cs, pos))
     _close(got, want, atol=0.01)
     for b in range(B):
@@ -329,10 +335,12 @@ def test_decode_attn_fused_rope(D, lens, chunk):
 
 
 @pytest.mark.parametrize("D", [64, 96, 128])
-@pytest.mark.parametrize("B,chunk", [(1, 512), (2, 256), (3, 1024), (1, 64)])
+@pytest.mark.parametrize("B,chunk", [(1, 512), (2, 256), (3, 1024), (1, 64), (1, 1024)])
 def test_decode_attn_prefetch_variant(D, B, chunk):
     """MHA decode with the next tile prefetched (B rows alone: B * Hkv <= 32) == the streaming variant
-    (the same rows inside a batch padded past 32 (row, kv head) pairs)."""
+    (the same rows inside a batch padded past 32 (row, kv head) pairs). B * H is a multiple of 8, so
+    the small launch exchanges its splits on one XCD: chunk <= 512 the MFMA kernel, chunk = 1024 the
+    prefetching VALU kernel's same-XCD form (8 and 24 pairs)."""
     torch.manual_seed(D + B)
     H, slots, max_seq = 8, 4, 2048
     kc, vc = _rand(slots, H, max_seq, D), _rand(slots, H, max_seq, D)
@@ -608,9 +616,11 @@ def test_kmeans_accum():
     assert torch.equal(c1, c2)
 
 
-@pytest.mark.parametrize("H,Hkv,D", [(32, 8, 128), (8, 1, 128), (16, 8, 64), (8, 2, 96)])
+@pytest.mark.parametrize("H,Hkv,D", [(32, 8, 128), (8, 1, 128), (16, 8, 64), (8, 2, 96), (4, 2, 96), (8, 1, 96),
+                                     (4, 2, 128), (8, 1, 64)])
 def test_decode_attn_gqa(H, Hkv, D):
-    """GQA decode: the MFMA kernel (D = 64 / 128) and the VALU kernel (other head dims) vs fp32."""
+    """GQA decode: the MFMA kernel (D = 64 / 128) and the VALU kernel (D = 96) vs fp32, every group
+    size (2, 4, 8) of each."""
     torch.manual_seed(7)
     B, S = 4, 1500
     kc, vc = _rand(4, Hkv, S, D), _rand(4, Hkv, S, D)
