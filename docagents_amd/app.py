@@ -50,7 +50,8 @@ def local_engine(cfg: Config):
                                ivf_lists=cfg.ivf_lists, ivf_probes=cfg.ivf_probes,
                                enc_dtype="fp8" if cfg.dtype == "fp8" else "bf16",
                                llm_weight_dtype=cfg.llm_weight_dtype, kv_cache_dtype=cfg.kv_cache_dtype,
-                               index_dtype=cfg.index_dtype, max_seq=4096 if dev == "cuda" else 1024)
+                               index_dtype=cfg.index_dtype, llm_prefill_dtype=cfg.llm_prefill_dtype,
+                               max_seq=4096 if dev == "cuda" else 1024)
     return _ENGINES[key]
 
 

@@ -57,6 +57,10 @@ class Config:
     # decoder KV-cache storage: bf16, or fp8 = every cached K / V row as e4m3 codes + one power-of-two
     # fp32 scale (D + 4 bytes per row instead of 2 D): a throughput / capacity option (TP_SIZE=1 only)
     kv_cache_dtype: str = field(default="bf16", metadata={"env": "KV_CACHE_DTYPE"})
+    # decoder prefill products: bf16, or fp8 = W8A8 on the fp8 MFMA tile (activations quantised per token row
+    # to e4m3, weights the LLM_WEIGHT_DTYPE=fp8 copy; attention, norms' inputs, LM head and decode unchanged):
+    # needs LLM_WEIGHT_DTYPE=fp8 and TP_SIZE=1
+    llm_prefill_dtype: str = field(default="bf16", metadata={"env": "LLM_PREFILL_DTYPE"})
     tp_size: int = field(default=1, metadata={"env": "TP_SIZE"})
     index_shards: int = field(default=1, metadata={"env": "INDEX_SHARDS"})
     index_kind: str = field(default="flat", metadata={"env": "INDEX_KIND"})
@@ -148,6 +152,7 @@ class Config:
     ENGINE_DTYPES = ("bf16", "fp16", "fp8")
     LLM_WEIGHT_DTYPES = ("bf16", "fp8")
     KV_CACHE_DTYPES = ("bf16", "fp8")
+    LLM_PREFILL_DTYPES = ("bf16", "fp8")
     INDEX_DTYPES = ("bf16", "fp8")
 
     def validate_engine(self) -> "Config":
@@ -162,6 +167,14 @@ class Config:
         if self.llm_weight_dtype not in self.LLM_WEIGHT_DTYPES:
             raise ValueError(f"LLM_WEIGHT_DTYPE={self.llm_weight_dtype!r} is not supported "
                              f"(choose one of {', '.join(self.LLM_WEIGHT_DTYPES)})")
+        if self.llm_prefill_dtype not in self.LLM_PREFILL_DTYPES:
+            raise ValueError(f"LLM_PREFILL_DTYPE={self.llm_prefill_dtype!r} is not supported "
+                             f"(choose one of {', '.join(self.LLM_PREFILL_DTYPES)})")
+        if self.llm_prefill_dtype == "fp8" and self.llm_weight_dtype != "fp8":
+            # the weight side of the W8A8 products is the fp8 weight copy
+            raise ValueError("LLM_PREFILL_DTYPE=fp8 needs LLM_WEIGHT_DTYPE=fp8")
+        if self.llm_prefill_dtype == "fp8" and self.tp_size > 1:
+            raise ValueError("LLM_PREFILL_DTYPE=fp8 needs TP_SIZE=1")
         if self.llm_weight_dtype == "fp8" and self.tp_size > 1:
             # quantising per TP shard is a different model from quantising the whole
             raise ValueError("LLM_WEIGHT_DTYPE=fp8 needs TP_SIZE=1")

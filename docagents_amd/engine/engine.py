@@ -43,7 +43,8 @@ class Engine:
                  ivf_lists: int = 100, ivf_probes: int = 1, load_llm: bool = True, load_encoder: bool = True,
                  use_graphs: bool = True, embed_max_tokens: int = 65536, enc_dtype: str = "bf16",
                  share_prefix: bool = True, overlap_waves: bool = False, kv_cache_gb: float = 0.0,
-                 llm_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16", index_dtype: str = "bf16"):
+                 llm_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16", index_dtype: str = "bf16",
+                 llm_prefill_dtype: str = "bf16"):
         self.device = torch.device(device)
         self.lock = threading.RLock()      # the decoder / generator (one GPU thread drives it)
         self.enc_lock = threading.RLock()  # the encoder: the fast embed lane and the batcher share it
@@ -69,8 +70,9 @@ class Engine:
             # decode GEMVs stream; auto_batch below sizes the KV cache from what is free after it
             # kv_cache_dtype "fp8": the KV cache as e4m3 codes + a scale per row (D + 4 bytes instead of
             # 2 D); auto_batch sizes the cache with that row size
+            # llm_prefill_dtype "fp8": prefill products on the fp8 MFMA tile over that e4m3 weight copy
             self.decoder = LlamaDecoder(self.dec_cfg, self.device, seed=seed, tp=tp, weight_dtype=llm_weight_dtype,
-                                        kv_dtype=kv_cache_dtype)
+                                        kv_dtype=kv_cache_dtype, prefill_dtype=llm_prefill_dtype)
             if max_batch <= 0:
                 max_batch = self.auto_batch(max_seq, overlap_waves, kv_gb=kv_cache_gb)
             # + 1 dummy slot (padded graph rows) + 2 prompt-head slots (ContinuousScheduler heads)

@@ -16,6 +16,12 @@ N6-N8). Per layer (hidden state x is the residual stream, updated in place):
     g   = silu(h Wg^T) * (h Wu^T)                      ONE GEMM with the fused SwiGLU epilogue
     x   = x + g @ Wdown^T                              GEMM + residual (row-parallel + all-reduce)
 
+prefill_dtype="fp8" (W8A8 prefill; needs weight_dtype="fp8", TP 1): the four products of a prefill
+layer run e4m3 x e4m3 on the 256x256 fp8 MFMA tile (ops.gemm_fp8) where ops.prefill_w8_fusable takes
+them: rmsnorm_q8 (norm + per-token quantisation, no bf16 h) feeds QKV and gate/up, quant_fp8 feeds O
+and down, RoPE and the cache write are the separate rope_cache / rope_cache_kv8 launch. Attention,
+the residual stream, the LM head and every decode step are unchanged.
+
 TP layout (rank r of t): local q/k/v heads, F/t FFN features, vocab-parallel lm_head. Generation
 never gathers the [B, V/t] logits: each rank reduces its slice to 8 floats per row (best Gumbel
 score + its global index, local max, local sum-exp, the best's logit) and one tiny gather of those
@@ -42,6 +48,7 @@ _FUSED_ROPE_DECODE = True
 # read (one per sequence); its K / V cache writes still cover every token (DA_PREFILL_TAIL=0: every
 # row through the whole layer; the tests compare both, bit for bit).
 _PREFILL_TAIL = os.environ.get("DA_PREFILL_TAIL", "1") != "0"
+_PF8_ANY_M = 1 << 20  # a row count above every row threshold of ops.prefill_w8_fusable: "at some prefill size"
 
 
 class TPContext:
@@ -248,6 +255,7 @@ class KVCache:
 
 
 WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMVs and the 2..32-row gemm_dk steps
+PREFILL_DTYPES = ("bf16", "fp8")  # fp8: prefill products as e4m3 x e4m3 on that copy, activations quantised per token
 
 
 class LlamaDecoder:
@@ -255,7 +263,8 @@ class LlamaDecoder:
     layer_hook = None   # prefill: called with the layer index before each layer (stream steering)
 
     def __init__(self, cfg: DecoderConfig, device="cuda", seed: int = 0, tp: TPContext | None = None,
-                 weights: dict | None = None, weight_dtype: str = "bf16", kv_dtype: str = "bf16"):
+                 weights: dict | None = None, weight_dtype: str = "bf16", kv_dtype: str = "bf16",
+                 prefill_dtype: str = "bf16"):
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype={weight_dtype!r} is not supported ({' | '.join(WEIGHT_DTYPES)})")
         if weight_dtype == "fp8" and tp is not None and tp.size > 1:
@@ -266,7 +275,15 @@ class LlamaDecoder:
         if kv_dtype == "fp8" and tp is not None and tp.size > 1:
             # per-head quantisation is shard-independent, but no TP test covers the combination yet
             raise ValueError("kv_dtype='fp8' needs TP size 1")
+        if prefill_dtype not in PREFILL_DTYPES:
+            raise ValueError(f"prefill_dtype={prefill_dtype!r} is not supported ({' | '.join(PREFILL_DTYPES)})")
+        if prefill_dtype == "fp8" and weight_dtype != "fp8":
+            # the weight side of W8A8 is the fp8 weight copy; without it the bf16 model is another model
+            raise ValueError("prefill_dtype='fp8' needs weight_dtype='fp8'")
+        if prefill_dtype == "fp8" and tp is not None and tp.size > 1:
+            raise ValueError("prefill_dtype='fp8' needs TP size 1")
         self.weight_dtype = weight_dtype
+        self.prefill_dtype = prefill_dtype  # "fp8": prefill products on ops.gemm_fp8 where the route takes them
         self.kv_dtype = kv_dtype  # "fp8": e4m3 KV cache (KVCache dtype); prefill / decode take the kv8 ops
         self.cfg = cfg
         self.device = torch.device(device)
@@ -304,8 +321,11 @@ class LlamaDecoder:
         values (exact in bf16), so prefill and the wider decode steps compute the same model the batch-1
         fp8 GEMVs and the 2..32-row fp8 gemm_dk steps stream at half the bytes. The fp8 copy ({name}_q8
         [N, K] e4m3, {name}_s8 [N] fp32) is kept only for the products ops.gemm_w8 or ops.gemm_dk_w8
-        accepts; the embedding and the norm gains stay bf16."""
+        accepts, and with prefill_dtype="fp8" for the layer products ops.prefill_w8_fusable accepts (the
+        LM head has at most 128 rows: never an fp8 prefill product); the embedding and the norm gains
+        stay bf16."""
         o = self.ops
+        pf8 = self.prefill_dtype == "fp8"
         prods = [(L, k, e) for L in self.w["layers"]
                  for k, e in (("wqkv", EPI_NONE), ("wo", EPI_RESID), ("w_gu", EPI_SWIGLU), ("w_down", EPI_RESID))]
         prods.append((self.w, "lm_head", EPI_NONE))
@@ -313,7 +333,8 @@ class LlamaDecoder:
             w = d[k]
             q, s = o.quant_weight_fp8_pow2(w)
             d[k] = (q.float() * s[:, None]).to(w.dtype).contiguous()
-            if o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi) or o.dk_w8_fusable(2, w.shape[0], w.shape[1], epi):
+            if (o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi) or o.dk_w8_fusable(2, w.shape[0], w.shape[1], epi)
+                    or (pf8 and d is not self.w and o.prefill_w8_fusable(_PF8_ANY_M, w.shape[0], w.shape[1], epi))):
                 d[k + "_q8"], d[k + "_s8"] = q, s
             del w, q, s
 
@@ -400,6 +421,60 @@ class LlamaDecoder:
         tp.all_reduce_(x)
         return x
 
+    def _pf8(self, d, name, M: int, epi: int) -> bool:
+        """True when the product on d[name] of a prefill over M rows runs on ops.gemm_fp8."""
+        w = d[name]
+        return (self.prefill_dtype == "fp8" and (name + "_q8") in d
+                and self.ops.prefill_w8_fusable(M, w.shape[0], w.shape[1], epi))
+
+    def _pf8_layer(self, M: int) -> bool:
+        """True when a prefill over M rows takes the fp8 layer body (any of its four products is routed
+        to ops.gemm_fp8); otherwise prefill() is the bf16 prefill, launch for launch."""
+        L = self.w["layers"][0]
+        return any(self._pf8(L, k, M, e) for k, e in (("wqkv", EPI_NONE), ("wo", EPI_RESID), ("w_gu", EPI_SWIGLU),
+                                                      ("w_down", EPI_RESID)))
+
+    def _qkv_w8(self, L, li: int, x, pos, slot_tok):
+        """fp8 prefill: RMSNorm + QKV projection + RoPE + KV-cache write, rotated qkv rows returned (the
+        attention reads the sequences' own k / v from them). rmsnorm_q8 -> gemm_fp8 where the route
+        takes the product, then the unfused cache write of either cache type."""
+        c, o, cache = self.cfg, self.ops, self.cache
+        if self._pf8(L, "wqkv", x.shape[0], EPI_NONE):
+            hq, hs = o.rmsnorm_q8(x, L["ln_attn"], c.eps)
+            qkv = o.gemm_fp8(hq, hs, L["wqkv_q8"], L["wqkv_s8"])
+        else:
+            qkv = o.gemm(o.rmsnorm(x, L["ln_attn"], c.eps), L["wqkv"])
+        if self.kv_dtype == "fp8":
+            kq, vq, ks, vs = cache.kv8(li)
+            return o.rope_cache_kv8(qkv, pos, self.cos_sin, self.hl, self.kl, c.head_dim, slot_tok, kq, vq, ks, vs)
+        return o.rope_cache(qkv, pos, self.cos_sin, self.hl, self.kl, c.head_dim, slot=slot_tok,
+                            k_cache=cache.k(li), v_cache=cache.v(li))
+
+    def _attn_out_and_mlp_w8(self, L, a, x, M: int, routes=None):
+        """_attn_out_and_mlp of an fp8 prefill (TP 1) for rows of a pass over M rows: all of them, or
+        the rows a last-layer tail keeps (``routes``: _tail_routes(M), for the products that stay on
+        gemm()). Each product asks the route with M, the norm sums in the M-row pass's order, and
+        quant_fp8 / gemm_fp8 treat every row on its own (per-row scales, one fixed tile, no split-K),
+        so a kept row ends with the bits the full pass gives it."""
+        o, c = self.ops, self.cfg
+        r_o, r_gu, r_down = routes if routes is not None else ({}, {}, {})
+        if self._pf8(L, "wo", M, EPI_RESID):
+            aq, sa = o.quant_fp8(a)
+            o.gemm_fp8(aq, sa, L["wo_q8"], L["wo_s8"], epi=EPI_RESID, resid=x, out=x)        # x += o, in place
+        else:
+            o.gemm(a, L["wo"], epi=EPI_RESID, resid=x, out=x, **r_o)
+        if self._pf8(L, "w_gu", M, EPI_SWIGLU):
+            hq, hs = o.rmsnorm_q8(x, L["ln_mlp"], c.eps, route_m=M)
+            g = o.gemm_fp8(hq, hs, L["w_gu_q8"], L["w_gu_s8"], epi=EPI_SWIGLU)
+        else:
+            g = o.gemm(o.rmsnorm(x, L["ln_mlp"], c.eps, route_m=M), L["w_gu"], epi=EPI_SWIGLU, **r_gu)
+        if self._pf8(L, "w_down", M, EPI_RESID):
+            gq, gs = o.quant_fp8(g)
+            o.gemm_fp8(gq, gs, L["w_down_q8"], L["w_down_s8"], epi=EPI_RESID, resid=x, out=x)  # x += mlp, in place
+        else:
+            o.gemm(g, L["w_down"], epi=EPI_RESID, resid=x, out=x, **r_down)
+        return x
+
     def _logits(self, hlast, gather: bool = True, out=None):
         """Logits of the rows of ``hlast``: the full [B, V] (gather=True; an all-gather of the vocab
         slices under TP) or this rank's slice [B, V/t] (gather=False: what ``sample`` consumes;
@@ -435,18 +510,29 @@ class LlamaDecoder:
         hook = self.layer_hook
         kv8 = self.kv_dtype == "fp8"
         # fp8 cache: the attention reads the sequences' own k / v from the (unquantised) qkv rows
-        kv_from_cache = not kv8 and bool(getattr(o, "flash_kv_cache_ok", lambda *_: False)(D, True))
         M, last = x.shape[0], len(self.w["layers"]) - 1
+        w8 = self._pf8_layer(M)  # fp8 prefill: the layer body below the bf16 one; k / v always from the qkv rows
+        kv_from_cache = not kv8 and not w8 and bool(getattr(o, "flash_kv_cache_ok", lambda *_: False)(D, True))
         # the last layer's hidden rows are read at last_idx only (its K / V rows by decode, from the
         # cache): past its QKV projection it runs on those rows alone, with the full pass's bits
         tail = self._tail_routes(M)
         for li, L in enumerate(self.w["layers"]):
             if hook is not None:  # e.g. move the rest of a prefill to another (CU-masked) stream
                 hook(li)
-            h = o.rmsnorm(x, L["ln_attn"], c.eps)
+            h = None if w8 else o.rmsnorm(x, L["ln_attn"], c.eps)
             # QKV projection + RoPE + KV-cache write in one kernel (gemm8p EPI_ROPE epilogue); where the
             # attention reads its keys from the cache (Phi-3's D = 96), k / v go to the cache only
-            if kv8:
+            if w8:
+                qkv = self._qkv_w8(L, li, x, pos, slot_tok)
+                if prefix is None:
+                    pre = None
+                elif kv8:
+                    kq, vq, ks, vs = cache.kv8(li)
+                    pre = (o.kv8_dequant(kq, ks, prefix[0], prefix[1]), o.kv8_dequant(vq, vs, prefix[0], prefix[1]),
+                           prefix[1])
+                else:
+                    pre = (cache.k(li)[prefix[0]], cache.v(li)[prefix[0]], prefix[1])
+            elif kv8:
                 # the unfused path gemm_rope takes for short prefills, with the quantising cache write;
                 # the shared prefix is dequantised (exactly) to bf16 for the flash kernel, per layer
                 kq, vq, ks, vs = cache.kv8(li)
@@ -467,9 +553,13 @@ class LlamaDecoder:
                                         max_seqlen, hl, kl, D, causal=True, prefix=pre, tail_only=cut)
             del qkv, h
             if cut:
-                x = self._attn_out_and_mlp_rows(L, a.index_select(0, last_idx), x.index_select(0, last_idx), tail, M)
+                a, x = a.index_select(0, last_idx), x.index_select(0, last_idx)
+                if w8:
+                    x = self._attn_out_and_mlp_w8(L, a, x, M, tail)
+                else:
+                    x = self._attn_out_and_mlp_rows(L, a, x, tail, M)
                 return self._logits(x, gather=not local_logits)
-            x = self._attn_out_and_mlp(L, a, x)
+            x = self._attn_out_and_mlp_w8(L, a, x, M) if w8 else self._attn_out_and_mlp(L, a, x)
         return self._logits(x.index_select(0, last_idx), gather=not local_logits)
 
     # ------------------------------------------------------------- decode (graph-capturable)

@@ -1,6 +1,14 @@
-// 256x256-tile fp8 GEMM for prefill-sized M (C[M,N] = epi(A[M,K] . W[N,K]^T)): the encoder's fp8
-// path (BASELINE config 5). bf16 prefill GEMMs run the phase-split gemm8p.hip kernel, which
-// replaced this kernel's bf16 instantiation (1.42-1.51 vs 1.23-1.33 PF/s, profiles/r2).
+// 256x256-tile fp8 GEMM for prefill-sized M (C[M,N] = epi(A[M,K] . W[N,K]^T)): the fp8 path of the
+// encoder (BASELINE config 5) and of the decoder's prefill (LLM_PREFILL_DTYPE=fp8: W8A8, per-token
+// activation scales from rmsnorm_q8 / quant_fp8_rows, the weight copy's per-row scales). bf16
+// prefill GEMMs run the phase-split gemm8p.hip kernel, which replaced this kernel's bf16
+// instantiation (1.42-1.51 vs 1.23-1.33 PF/s, profiles/r2).
+//
+// What the decoder relies on (tests/test_prefill8_gpu.py): any M >= 1 and any N % 8 == 0 (operand
+// rows past M / N are clamped loads whose results are never stored; a row's value depends on no
+// other row and on no M, there is no split-K), padded lda / ldc / ldr, EPI_RESID with C == resid
+// (each 16-B chunk is read and written by the same lane, once), and EPI_SWIGLU on w_gu's 16-row
+// gate / up interleave (fragment columns 2p = gate, 2p + 1 = up of output columns 16p..16p+15).
 //
 // fp8 (OCP e4m3): the same 128-byte K-step and LDS image (BK = 128 fp8), one
 // v_mfma_scale_f32_16x16x128_f8f6f4 per fragment pair instead of two bf16 16x16x32 (2x the bf16
@@ -237,6 +245,10 @@ DA_EXPORT int da_gemm_fp8(const void* A, int lda, const void* W, const void* sa,
                           const void* bias, const void* resid, int ldr, int M, int N, int K, int epi, void* stream) {
   if (K % 128 || N % 8 || lda % 16 || ldc % 8 || !sa || !sw) return (int)hipErrorInvalidValue;
   if (epi == EPI_SWIGLU && N % 32) return (int)hipErrorInvalidValue;
+  // every row of A, C and resid is moved 16 B at a time
+  if (M < 0 || lda < K || ldc < (epi == EPI_SWIGLU ? N / 2 : N) || ((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16)
+    return (int)hipErrorInvalidValue;
+  if (epi == EPI_RESID && (!resid || ldr % 8 || ldr < N || (uintptr_t)resid % 16)) return (int)hipErrorInvalidValue;
   if (M == 0) return 0;
   GemmArgs a{};
   a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C;

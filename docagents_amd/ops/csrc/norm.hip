@@ -352,6 +352,88 @@ __global__ void quant_fp8_rows_kernel(const bf16_t* __restrict__ x, int ldx, int
   }
 }
 
+// 8 floats rounded to bf16 and back: the values a bf16 store followed by a bf16 load would carry.
+__device__ __forceinline__ void round8_bf16(float (&v)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = bf2f(f2bf(v[e]));
+}
+
+// RMSNorm straight to e4m3 (the fp8 prefill's QKV and gate/up inputs): y = rms(x) * w rounded to
+// bf16 exactly as rmsnorm_kernel stores it, then quant_fp8_rows_kernel's rule on those values, the
+// row never leaving registers. Codes and scales are bit for bit quant_fp8(rmsnorm(x)); the bf16 row
+// is not written anywhere. Same summation order as rmsnorm_kernel (one workgroup per row).
+__global__ void rmsnorm_q8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                  unsigned char* __restrict__ yq, float* __restrict__ yscale, int D, float eps,
+                                  int ldx, int ldq) {
+  __shared__ float red[16];
+  const int row = blockIdx.x;
+  const bf16_t* xr = x + (size_t)row * ldx;
+  const int nch = D / 8;
+  float v[MAXCH][8];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXCH; ++i) {
+    const int c = threadIdx.x + i * blockDim.x;
+    if (c < nch) {
+      load8(xr + c * 8, v[i]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ss += v[i][e] * v[i][e];
+    }
+  }
+  ss = block_sum(ss, red);
+  const float inv = rsqrtf(ss / D + eps);
+#pragma unroll
+  for (int i = 0; i < MAXCH; ++i) {
+    const int c = threadIdx.x + i * blockDim.x;
+    if (c < nch) {
+      float wv[8];
+      load8(w + c * 8, wv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[i][e] = v[i][e] * inv * wv[e];
+      round8_bf16(v[i]);
+    }
+  }
+  store_row_fp8(v, nch, row, yq, ldq, yscale, red);
+}
+
+// The many-row form (one wave per row, as rmsnorm_rows_kernel and with its summation order): the
+// row maximum is a wave-level maximum, so there is no barrier at all.
+template <int NCH>
+__global__ void __launch_bounds__(256)
+rmsnorm_q8_rows_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, unsigned char* __restrict__ yq,
+                       float* __restrict__ yscale, int M, int D, float eps, int ldx, int ldq) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;  // whole wave: no barrier below
+  const bf16_t* xr = x + (size_t)row * ldx;
+  float v[NCH][8];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) load8(xr + (i * 64 + lane) * 8, v[i]);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss += v[i][e] * v[i][e];
+  ss = wave_sum(ss);
+  const float inv = rsqrtf(ss / D + eps);
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    float wv[8];
+    load8(w + (i * 64 + lane) * 8, wv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[i][e] = v[i][e] * inv * wv[e];
+    round8_bf16(v[i]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[i][e]));
+  }
+  amax = wave_max(amax);
+  const float sc = amax > 0.f ? amax / 448.f : 1.f;
+  const float qinv = 1.f / sc;
+  if (lane == 0) yscale[row] = sc;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) *(u32x2_t*)(yq + (size_t)row * ldq + (i * 64 + lane) * 8) = f32x8_fp8(v[i], qinv);
+}
+
 static inline int row_threads(int D) {
   int ch = D / 8;
   int t = ((ch + 63) / 64) * 64;
@@ -442,6 +524,32 @@ DA_EXPORT int da_quant_fp8_rows(const void* x, int ldx, int M, int K, void* out,
   if (M == 0) return 0;
   quant_fp8_rows_kernel<<<M, row_threads(K), 0, (hipStream_t)stream>>>((const bf16_t*)x, ldx, K, (unsigned char*)out,
                                                                        ldo, (float*)scale);
+  DA_LAUNCH_CHECK();
+}
+
+// RMSNorm + per-row e4m3 quantisation in one pass: codes [M, ldo] and scales [M], no bf16 output.
+// Routed like rmsnorm_launch (route_m as da_rmsnorm_routed: the row count of the pass the rows
+// belong to), so the result is bit for bit da_quant_fp8_rows(da_rmsnorm_routed(x)).
+DA_EXPORT int da_rmsnorm_q8(const void* x, int ldx, const void* w, void* out, int ldo, void* scale, int M, int D,
+                            float eps, int route_m, void* stream) {
+  if (!d_ok(D) || ldx % 8 || ldo % 8 || ldx < D || ldo < D || !out || !scale) return (int)hipErrorInvalidValue;
+  if (M == 0) return 0;
+  if (route_m < M) route_m = M;
+  const int nch = D / 512;  // the widths rmsnorm_launch gives the one-wave-per-row kernel
+  if (route_m >= 1024 && D % 512 == 0 && (nch == 4 || nch == 6 || nch == 8)) {
+    const dim3 grid((M + 3) / 4);
+#define RMS_Q8_ROWS(N) rmsnorm_q8_rows_kernel<N><<<grid, 256, 0, (hipStream_t)stream>>>(                        \
+                         (const bf16_t*)x, (const bf16_t*)w, (unsigned char*)out, (float*)scale, M, D, eps, ldx, ldo)
+    switch (nch) {
+      case 4: RMS_Q8_ROWS(4); break;
+      case 6: RMS_Q8_ROWS(6); break;
+      default: RMS_Q8_ROWS(8); break;
+    }
+#undef RMS_Q8_ROWS
+    DA_LAUNCH_CHECK();
+  }
+  rmsnorm_q8_kernel<<<M, row_threads(D), 0, (hipStream_t)stream>>>((const bf16_t*)x, (const bf16_t*)w,
+                                                                    (unsigned char*)out, (float*)scale, D, eps, ldx, ldo);
   DA_LAUNCH_CHECK();
 }
 

@@ -190,6 +190,32 @@ def plan_dk_w8(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
     return GemmPlan("dk_w8", TILE_DK, 1, 0)
 
 
+# Prefill products on the fp8 256x256 tile (csrc/gemm256.hip, da_gemm_fp8; LLM_PREFILL_DTYPE=fp8):
+# e4m3 activations quantised per token row x the decoder's e4m3 weight copy. Rows up to 128 are a
+# decode step's and keep the routes above.
+PREFILL_W8_ABOVE = 128
+
+
+def prefill_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
+    """True when an fp8 prefill (prefill_dtype="fp8") runs the product of an M-row pass on
+    da_gemm_fp8 instead of gemm(): every shape the kernel takes above the decode range. The rows a
+    last-layer tail keeps follow the route of the M-row pass they belong to (the caller asks with
+    that M), so a kept row ends with the bits the full pass gives it: the tile is fixed, there is no
+    split-K and the scales are per row, so a row's result does not depend on M. Which shapes were
+    measured against the bf16 route and which are taken on the rule alone: profiles/prefill8/README.md.
+
+    Held back, from that A/B: an EPI_RESID product (its input needs a quantisation pass of its own;
+    rmsnorm_q8 replaces a norm pass that runs anyway) from PREFILL_M rows whose 256x256 tiles do not
+    fill the 256 CUs once and whose K is at most 3072. There the tile's K loop is too short for the
+    fp8 MFMA rate to pay for the pass: Phi-3's O projection in a batch-1 prefill (M = 2930, 144 tiles)
+    ran 55.8 us against 55.2 us on the bf16 route; the down projection (same tiles, K = 8192) won."""
+    if not (M > PREFILL_W8_ABOVE and K % 128 == 0 and N % 8 == 0 and epi in (EPI_NONE, EPI_SWIGLU, EPI_RESID)
+            and (epi != EPI_SWIGLU or N % 32 == 0)):
+        return False
+    underfilled = -(-M // 256) * -(-N // 256) < 256
+    return not (epi == EPI_RESID and M >= PREFILL_M and underfilled and K <= 3072)
+
+
 def plan_resid_norm(M: int, N: int, K: int, tile: int = 0, splits: int = 0) -> GemmPlan:
     """gemm_resid_norm()'s launch (M <= 128): the fused reduce + norm always reads fp32 partials, so
     the workspace is needed at one split too; above 64 rows it takes the 128x64 tile only."""

@@ -19,7 +19,7 @@ import torch
 
 from . import gemm_plan
 from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: F401 - re-exported
-                        gemv_fusable, gemv_w8_fusable)
+                        gemv_fusable, gemv_w8_fusable, prefill_w8_fusable)
 from .reference import quant_weight_fp8, quant_weight_fp8_pow2  # noqa: F401 - host-side torch, done once at load
 
 _LIB = None
@@ -53,6 +53,7 @@ _SIGS = {
     "da_rmsnorm": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
     "da_rmsnorm_routed": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
                           c_void_p],
+    "da_rmsnorm_q8": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p],
     "da_swiglu_interleaved": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     "da_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "da_bert_embed_ln": [c_void_p] * 9 + [c_int, c_int, c_float, c_void_p],
@@ -473,30 +474,55 @@ def gemm_dk_w8(a, wq, sw, epi: int = EPI_NONE, bias=None, resid=None, out=None, 
 
 
 def gemm_fp8(aq, sa, wq, sw, bias=None, epi: int = EPI_NONE, resid=None, out=None) -> torch.Tensor:
-    """out[M, N] = epi((aq . wq^T) * sa[:, None] * sw[None, :]) with e4m3 operands (256x256 MFMA tile)."""
-    _req(aq.is_cuda and aq.dtype == FP8 and wq.dtype == FP8, "fp8 operands expected")
+    """out[M, N'] = epi((aq . wq^T) * sa[:, None] * sw[None, :]) with e4m3 operands (256x256 MFMA tile; N' = N/2
+    for EPI_SWIGLU on 16-row gate / up interleaved weights). Any M; rows may be padded (aq, out, resid strides).
+    EPI_RESID may add in place (``out is resid``): every element is read and written by the same lane."""
+    _req(aq.is_cuda and wq.is_cuda and aq.dtype == FP8 and wq.dtype == FP8, "fp8 operands expected")
+    _req(aq.dim() == 2 and wq.dim() == 2, "gemm_fp8 expects 2-D operands")
     M, K = aq.shape
     N, K2 = wq.shape
     _req(K == K2 and K % 128 == 0 and N % 8 == 0, f"fp8 gemm shape M={M} N={N} K={K}")
-    _req(aq.stride(1) == 1 and aq.stride(0) % 16 == 0 and wq.is_contiguous(), "fp8 operand layout")
+    _req(epi in (EPI_NONE, EPI_BIAS, EPI_GELU, EPI_SWIGLU, EPI_RESID), f"gemm_fp8 has no epilogue {epi}")
+    _req(epi != EPI_SWIGLU or N % 32 == 0, f"fp8 gemm SwiGLU needs N % 32 == 0, got N={N}")
+    _req(aq.stride(1) == 1 and aq.stride(0) % 16 == 0 and aq.stride(0) >= K and wq.is_contiguous(),
+         "fp8 operand layout")
     _req(aq.data_ptr() % 16 == 0 and wq.data_ptr() % 16 == 0, "operands must be 16-B aligned")
-    _req(sa.dtype == torch.float32 and sa.numel() >= M and sw.dtype == torch.float32 and sw.numel() == N, "scales")
+    _req(sa.is_cuda and sw.is_cuda and sa.dtype == torch.float32 and sa.is_contiguous() and sa.numel() >= M
+         and sw.dtype == torch.float32 and sw.is_contiguous() and sw.numel() == N, "scales")
     nout = N // 2 if epi == EPI_SWIGLU else N
     if out is None:
         out = torch.empty((M, nout), dtype=torch.bfloat16, device=aq.device)
     _bf16_cuda(out, "out")
-    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0, "bad out")
+    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0 and out.stride(0) >= nout
+         and out.data_ptr() % 16 == 0, "bad out")
     if bias is not None:
-        _bf16_cuda(bias, "bias"); _req(bias.numel() == N, "bias must be [N]")
+        _bf16_cuda(bias, "bias"); _req(bias.numel() == N and bias.is_contiguous(), "bias must be [N]")
     ldr = 0
     if epi == EPI_RESID:
-        _req(resid is not None and resid.shape == (M, N) and resid.stride(1) == 1, "bad resid")
+        _req(resid is not None, "EPI_RESID needs resid")
+        _bf16_cuda(resid, "resid")
+        _req(resid.shape == (M, N) and resid.stride(1) == 1 and resid.stride(0) % 8 == 0 and resid.stride(0) >= N
+             and resid.data_ptr() % 16 == 0, "bad resid")
+        # in place is the same tensor; a resid that overlaps out any other way would be read after a write
+        _req(resid.data_ptr() == out.data_ptr() and resid.stride(0) == out.stride(0)
+             or not _overlap(resid, out), "resid may alias out only as the same rows")
         ldr = resid.stride(0)
+    else:
+        resid = None
     if M == 0:
         return out
     _check(lib().da_gemm_fp8(_ptr(aq), aq.stride(0), _ptr(wq), _ptr(sa), _ptr(sw), _ptr(out), out.stride(0),
                              _ptr(bias), _ptr(resid), ldr, M, N, K, epi, _stream()), "gemm_fp8")
     return out
+
+
+def _overlap(a, b) -> bool:
+    """True when the byte ranges spanned by two row-major 2-D tensors intersect."""
+    def span(t):
+        n = (t.shape[0] - 1) * t.stride(0) + t.shape[1] if t.numel() else 0
+        return t.data_ptr(), t.data_ptr() + n * t.element_size()
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
 
 
 def gemm_resid_norm(a, w, resid, gamma, eps: float, out=None, h_out=None, bias=None, tile: int = 0, splits: int = 0):
@@ -537,6 +563,28 @@ def rmsnorm(x, w, eps: float, resid=None, out=None, route_m: int = 0):
     _check(lib().da_rmsnorm_routed(_ptr(x), x.stride(0), _ptr(resid), _ptr(w), _ptr(out), out.stride(0), M, D,
                                    float(eps), int(route_m), _stream()), "rmsnorm")
     return out
+
+
+def rmsnorm_q8(x, g, eps: float, out=None, scale=None, route_m: int = 0):
+    """RMSNorm straight to e4m3: (codes [M, D] float8_e4m3fn, scale [M] fp32), bit for bit
+    quant_fp8(rmsnorm(x, g, eps, route_m=route_m)) in one pass that writes no bf16 row."""
+    _bf16_cuda(x, "x"); _bf16_cuda(g, "g")
+    _req(x.dim() == 2, "rmsnorm_q8 expects [M, D] rows")
+    M, D = x.shape
+    _req(x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= D and D % 8 == 0 and 0 < D <= 16384
+         and x.data_ptr() % 16 == 0, "x must be row-major, D % 8 == 0, D <= 16384, 16-B aligned rows")
+    _req(g.numel() == D and g.is_contiguous() and g.data_ptr() % 16 == 0, "g must be [D]")
+    _req(eps > 0, "rmsnorm_q8 needs eps > 0")
+    if out is None:
+        out = torch.empty((M, D), dtype=FP8, device=x.device)
+    if scale is None:
+        scale = torch.empty(M, dtype=torch.float32, device=x.device)
+    _req(out.is_cuda and out.dtype == FP8 and out.shape == (M, D) and out.stride(1) == 1 and out.stride(0) % 16 == 0
+         and out.stride(0) >= D and out.data_ptr() % 16 == 0, "bad out")
+    _req(scale.is_cuda and scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() >= M, "bad scale")
+    _check(lib().da_rmsnorm_q8(_ptr(x), x.stride(0), _ptr(g), _ptr(out), out.stride(0), _ptr(scale), M, D, float(eps),
+                               int(route_m), _stream()), "rmsnorm_q8")
+    return out, scale
 
 
 def layernorm(x, g, b, eps: float, resid=None, out=None, fp8_out: bool = False):

@@ -477,6 +477,18 @@ def gemm_fp8(aq, sa, wq, sw, bias=None, epi=EPI_NONE, resid=None, out=None):
     return _epilogue(y, wq.shape[0], bias, epi, resid, out)
 
 
+def rmsnorm_q8(x, g, eps, out=None, scale=None, route_m=0):
+    """fp32 oracle of kernels.rmsnorm_q8: the normalised row rounded to bf16 (rmsnorm), then
+    quant_fp8's per-row rule -> (codes [M, D] float8_e4m3fn, scale [M] fp32)."""
+    return quant_fp8(rmsnorm(x, g, eps), out=out, scale=scale)
+
+
+def prefill_w8_fusable(M, N, K, epi=EPI_NONE):
+    """gemm_plan.prefill_w8_fusable: the CPU decoder runs the same W8A8 products the GPU one does."""
+    from .gemm_plan import prefill_w8_fusable as f
+    return f(M, N, K, epi)
+
+
 def quant_weight_fp8(w):
     """Per-output-channel e4m3 weight quantisation (host-side torch; done once at load)."""
     wf = w.float()

@@ -109,7 +109,7 @@ def main(argv=None) -> int:
                  summary_max_new=cfg.summary_max_new_tokens, index_kind=cfg.index_kind, ivf_lists=cfg.ivf_lists,
                  ivf_probes=cfg.ivf_probes, max_seq=4096 if dev.type == "cuda" else 1024,
                  enc_dtype=cfg.dtype, llm_weight_dtype=cfg.llm_weight_dtype, kv_cache_dtype=cfg.kv_cache_dtype,
-                 index_dtype=cfg.index_dtype)
+                 index_dtype=cfg.index_dtype, llm_prefill_dtype=cfg.llm_prefill_dtype)
     if cfg.engine_admit_tokens > 0:
         eng.admit_tokens = cfg.engine_admit_tokens
     if cfg.engine_continuous and dev.type == "cuda" and eng.gen is not None:
