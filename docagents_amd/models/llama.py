@@ -48,6 +48,7 @@ _FUSED_ROPE_DECODE = True
 # read (one per sequence); its K / V cache writes still cover every token (DA_PREFILL_TAIL=0: every
 # row through the whole layer; the tests compare both, bit for bit).
 _PREFILL_TAIL = os.environ.get("DA_PREFILL_TAIL", "1") != "0"
+_MID_W8_ANY_M = 64  # a row count inside ops.tile_w8_fusable's range: "at some 33..128-row decode step"
 _PF8_ANY_M = 1 << 20  # a row count above every row threshold of ops.prefill_w8_fusable: "at some prefill size"
 
 
@@ -254,7 +255,7 @@ class KVCache:
         return cfg.layers * 2 * slots * (cfg.kv_heads // tp_size) * max_seq * row
 
 
-WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMVs and the 2..32-row gemm_dk steps
+WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMVs and the 2..128-row decode steps
 PREFILL_DTYPES = ("bf16", "fp8")  # fp8: prefill products as e4m3 x e4m3 on that copy, activations quantised per token
 
 
@@ -319,11 +320,11 @@ class LlamaDecoder:
         """weight_dtype="fp8": the model IS the quantised model. Every matmul weight is quantised per
         output row to e4m3 with a power-of-two scale and the bf16 tensor is replaced by the dequantised
         values (exact in bf16), so prefill and the wider decode steps compute the same model the batch-1
-        fp8 GEMVs and the 2..32-row fp8 gemm_dk steps stream at half the bytes. The fp8 copy ({name}_q8
-        [N, K] e4m3, {name}_s8 [N] fp32) is kept only for the products ops.gemm_w8 or ops.gemm_dk_w8
-        accepts, and with prefill_dtype="fp8" for the layer products ops.prefill_w8_fusable accepts (the
-        LM head has at most 128 rows: never an fp8 prefill product); the embedding and the norm gains
-        stay bf16."""
+        fp8 GEMVs and the 2..128-row fp8 decode steps stream at half the bytes. The fp8 copy ({name}_q8
+        [N, K] e4m3, {name}_s8 [N] fp32) is kept only for the products ops.gemm_w8, ops.gemm_dk_w8 or the
+        33..128-row ops (ops.tile_w8_fusable) accept, and with prefill_dtype="fp8" for the layer products
+        ops.prefill_w8_fusable accepts (the LM head has at most 128 rows: never an fp8 prefill product);
+        the embedding and the norm gains stay bf16."""
         o = self.ops
         pf8 = self.prefill_dtype == "fp8"
         prods = [(L, k, e) for L in self.w["layers"]
@@ -334,6 +335,7 @@ class LlamaDecoder:
             q, s = o.quant_weight_fp8_pow2(w)
             d[k] = (q.float() * s[:, None]).to(w.dtype).contiguous()
             if (o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi) or o.dk_w8_fusable(2, w.shape[0], w.shape[1], epi)
+                    or o.tile_w8_fusable(_MID_W8_ANY_M, w.shape[0], w.shape[1], epi)
                     or (pf8 and d is not self.w and o.prefill_w8_fusable(_PF8_ANY_M, w.shape[0], w.shape[1], epi))):
                 d[k + "_q8"], d[k + "_s8"] = q, s
             del w, q, s
@@ -353,13 +355,39 @@ class LlamaDecoder:
         return (self.weight_dtype == "fp8" and (name + "_q8") in d
                 and self.ops.dk_w8_fusable(B, w.shape[0], w.shape[1], epi))
 
+    def _mid_w8(self, d, name, B: int, epi: int) -> bool:
+        """True when the product on d[name] of a 33..128-row decode step streams the fp8 copy
+        (ops.gemm_tile_w8 / gemm_dk_splitk_w8 / gemm_resid_norm_w8)."""
+        w = d[name]
+        return (self.weight_dtype == "fp8" and (name + "_q8") in d
+                and self.ops.tile_w8_fusable(B, w.shape[0], w.shape[1], epi))
+
     def _gemm_dk1(self, d, name, a, epi: int = EPI_NONE, **kw):
-        """The product a @ d[name]^T of a gemm_dk decode layer: gemm_dk_w8 on the fp8 copy at 2..32
-        rows where the weight has one (weight_dtype="fp8"), today's ops.gemm_dk on the bf16 tensor
-        otherwise."""
+        """The product a @ d[name]^T of a gemm_dk decode layer on the fp8 copy where the weight has one
+        (weight_dtype="fp8"): gemm_dk_w8 at 2..32 rows, gemm_dk_splitk_w8 at 33..64 rows (the split-K
+        route; a producer of row sums is on it only with one part per 512 columns, as gemm_dk's is).
+        Today's ops.gemm_dk on the bf16 tensor otherwise."""
         if self._dk_w8(d, name, a.shape[0], epi):
             return self.ops.gemm_dk_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
+        if (self._mid_w8(d, name, a.shape[0], epi) and a.shape[0] <= self.ops.DK_MAX_M
+                and (kw.get("ssq_out") is None or d[name].shape[0] % 512 == 0)):
+            return self.ops.gemm_dk_splitk_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
         return self.ops.gemm_dk(a, d[name], epi=epi, **kw)
+
+    def _gemm_mid1(self, d, name, a, epi: int = EPI_NONE, **kw):
+        """The product a @ d[name]^T of a fused-norm decode layer: gemm_tile_w8 on the fp8 copy at 33..128
+        rows where the weight has one (weight_dtype="fp8"), today's ops.gemm on the bf16 tensor otherwise."""
+        if self._mid_w8(d, name, a.shape[0], epi):
+            return self.ops.gemm_tile_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
+        return self.ops.gemm(a, d[name], epi=epi, **kw)
+
+    def _resid_norm_mid1(self, d, name, a, x, gamma, h_out):
+        """x += a @ d[name]^T and h_out = RMSNorm(x) * gamma of a fused-norm decode layer, on the fp8
+        copy at 33..128 rows as _gemm_mid1."""
+        if self._mid_w8(d, name, a.shape[0], EPI_RESID):
+            return self.ops.gemm_resid_norm_w8(a, d[name + "_q8"], d[name + "_s8"], x, gamma, self.cfg.eps, out=x,
+                                               h_out=h_out)
+        return self.ops.gemm_resid_norm(a, d[name], x, gamma, self.cfg.eps, out=x, h_out=h_out)
 
     def _gain(self, g):
         """The gain a fused batch-1 GEMV norm streams: none once the gains are folded."""
@@ -652,15 +680,16 @@ class LlamaDecoder:
         c, o, cache = self.cfg, self.ops, self.cache
         D, hl, kl = c.head_dim, self.hl, self.kl
         layers = self.w["layers"]
+        mm, rn = self._gemm_mid1, self._resid_norm_mid1  # 33..128 rows, weight_dtype="fp8": the e4m3 copy
         h = o.rmsnorm(x, layers[0]["ln_attn"], c.eps, out=st.h)
         for li, L in enumerate(layers):
-            qkv = o.gemm(h, L["wqkv"], out=st.qkv)
+            qkv = mm(L, "wqkv", h, out=st.qkv)
             a = self._decode_attn(qkv, li, st)
-            h = o.gemm_resid_norm(a, L["wo"], x, L["ln_mlp"], c.eps, out=x, h_out=st.h)      # x += o; h = norm(x)
-            g = o.gemm(h, L["w_gu"], epi=EPI_SWIGLU)
+            h = rn(L, "wo", a, x, L["ln_mlp"], st.h)                                      # x += o; h = norm(x)
+            g = mm(L, "w_gu", h, epi=EPI_SWIGLU)
             nxt = layers[li + 1]["ln_attn"] if li + 1 < len(layers) else self.w["norm"]
-            h = o.gemm_resid_norm(g, L["w_down"], x, nxt, c.eps, out=x, h_out=st.h)       # x += mlp; h = norm(x)
-        st.logits.copy_(o.gemm(h, self.w["lm_head"]))  # h already carries the final norm
+            h = rn(L, "w_down", g, x, nxt, st.h)                                          # x += mlp; h = norm(x)
+        st.logits.copy_(mm(self.w, "lm_head", h))  # h already carries the final norm
         o.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
                  active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
         return st.tokens

@@ -38,3 +38,6 @@ int launch_gemm256(const GemmArgs& a, int epi, hipStream_t s, int fp8 = 1);
 int launch_gemm8p(const GemmArgs& a, int epi, hipStream_t s, int bm = 256);
 // four-wave 256x256 kernel (gemm4w.hip, 128x128 per wave; the tile-13 A/B arm), bf16, no EPI_ROPE
 int launch_gemm4w(const GemmArgs& a, int epi, hipStream_t s);
+// tiles 2 (64x128) and 9 (128x64) on e4m3 weights (gemm_tile_w8.hip): a.W holds the codes ([N, K] bytes),
+// a.sw the fp32 row scales; 1 <= M <= 128, K % 64 == 0, epi NONE / BIAS / SWIGLU / RESID / PARTIAL
+int launch_gemm_tile_w8(const GemmArgs& a, int tile, int epi, int splits, hipStream_t s);

@@ -13,211 +13,14 @@
 //  * epilogue staged through LDS in fp32, then 16-B coalesced stores with bias / GELU / SwiGLU /
 //    residual fused (the reference outsources all of this to OpenAI).
 //  * split-K writes fp32 partials; gemm_splitk_reduce applies the same epilogue.
+#include "fp8.h"
 #include "gemm.h"
 
 template <int BM, int BN, int WM, int WN, int EPI, int PF = 1>
 __global__ void __launch_bounds__(256)
 gemm_bf16_kernel(GemmArgs p) {
-  // PF = k-tiles in flight in registers. PF = 1: the classic register-staged double buffer (one
-  // tile ahead). Decode-sized tiles (M <= 64) stream weights and are latency-bound at PF = 1 —
-  // one 16-KB W tile per workgroup in flight, ~6 dependent HBM round trips per split — so they
-  // keep PF tiles (up to 72 KB per workgroup) requested ahead of the MFMAs (Little's law).
-  // (Weight fragments loaded straight into the MFMA B registers, skipping LDS, lost on every arm
-  // measured: half-line requests, profiles/r3/rejected_r3.txt.)
-  constexpr int BK = 64;
-  constexpr int TM = BM / WM, TN = BN / WN;
-  constexpr int FM = TM / 16, FN = TN / 16;
-  constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
-  constexpr int LA = BM * 8 / 256, LB = BN * 8 / 256;  // 16-B loads per thread per tile
-  static_assert(WM * WN == 4, "4 waves");
-  static_assert(LA >= 1 && LB >= 1, "tile too small");
-  constexpr int STAGE_FLOATS = 4 * TM * (TN + 4);
-  constexpr int LDS_MAIN = 2 * (A_BYTES + B_BYTES);
-  constexpr int LDS_BYTES = LDS_MAIN > STAGE_FLOATS * 4 ? LDS_MAIN : STAGE_FLOATS * 4;
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-
-  // ---- tile scheduling: XCD remap, then grouped-M ordering ----
-  const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  const int nwg = ntm * ntn;
-  const int t = xcd_remap(blockIdx.x, nwg);
-  constexpr int GROUP = 8;
-  const int gid = t / (GROUP * ntn);
-  const int first_m = gid * GROUP;
-  const int gsz = min(ntm - first_m, GROUP);
-  const int tin = t % (GROUP * ntn);
-  const int tm = first_m + tin % gsz, tn = tin / gsz;
-  const int m0 = tm * BM, n0 = tn * BN;
-
-  const int kbeg = blockIdx.z * p.k_per_split;
-  const int nk = p.k_per_split / BK;
-
-  // ---- global -> register staging (PF slots) ----
-  u32x4_t ra[PF][LA], rb[PF][LB];
-  const int fr = lane & 15, fg = lane >> 4;
-  // Rows past M / N are clamped, not branched around: they only feed accumulators whose outputs
-  // are never stored, and branch-free loads keep the compiler's vmcnt waits counted (a load
-  // under a divergent branch makes every later wait a full vmcnt(0) drain).
-  auto gload = [&](u32x4_t (&xa)[LA], u32x4_t (&xb)[LB], int kt) {
-    const int k0 = kbeg + kt * BK;
-#pragma unroll
-    for (int i = 0; i < LA; ++i) {
-      const int idx = tid + 256 * i, r = idx >> 3, c = idx & 7;
-      xa[i] = *(const u32x4_t*)(p.A + (size_t)min(m0 + r, p.M - 1) * p.lda + k0 + c * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < LB; ++i) {
-      const int idx = tid + 256 * i, r = idx >> 3, c = idx & 7;
-      xb[i] = *(const u32x4_t*)(p.W + (size_t)min(n0 + r, p.N - 1) * p.K + k0 + c * 8);
-    }
-  };
-  auto lstore = [&](const u32x4_t (&xa)[LA], const u32x4_t (&xb)[LB], int buf) {
-    char* sa = smem + buf * (A_BYTES + B_BYTES);
-    char* sb = sa + A_BYTES;
-#pragma unroll
-    for (int i = 0; i < LA; ++i) {
-      const int idx = tid + 256 * i, r = idx >> 3, c = idx & 7;
-      *(u32x4_t*)(sa + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = xa[i];
-    }
-#pragma unroll
-    for (int i = 0; i < LB; ++i) {
-      const int idx = tid + 256 * i, r = idx >> 3, c = idx & 7;
-      *(u32x4_t*)(sb + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = xb[i];
-    }
-  };
-
-  f32x4_t acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  // Loads are issued unconditionally (tile index clamped to nk - 1: the redundant tail loads hit
-  // L2) so every vmcnt wait below stays counted; compute / LDS stores sit under uniform branches.
-  const int kl = nk > 0 ? nk - 1 : 0;
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    gload(ra[u], rb[u], min(u, kl));
-    asm volatile("" ::: "memory");  // keep issue order = tile order (counted waits stay short)
-  }
-  if (nk > 0) lstore(ra[0], rb[0], 0);
-  __syncthreads();
-
-  for (int kt0 = 0; kt0 < nk; kt0 += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      const int kt = kt0 + u;
-      const int cur = kt & 1;
-      // slot u held tile kt, already copied to LDS: refill it PF tiles ahead
-      if (PF > 1 || kt + 1 < nk) gload(ra[u], rb[u], min(kt + PF, kl));
-      if (kt < nk) {
-        const char* sa = smem + cur * (A_BYTES + B_BYTES);
-        const char* sb = sa + A_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int c = kk * 4 + fg;
-          bf16x8_t af[FM], bfr[FN];
-#pragma unroll
-          for (int i = 0; i < FM; ++i) {
-            const int r = wm * TM + i * 16 + fr;
-            af[i] = *(const bf16x8_t*)(sa + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-          }
-#pragma unroll
-          for (int j = 0; j < FN; ++j) {
-            const int r = wn * TN + j * 16 + fr;
-            bfr[j] = *(const bf16x8_t*)(sb + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-          }
-#pragma unroll
-          for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(af[i], bfr[j], acc[i][j]);
-        }
-      }
-      if (kt >= nk) continue;
-      if (kt + 1 < nk) lstore(ra[(u + 1) % PF], rb[(u + 1) % PF], cur ^ 1);
-      // LDS writes visible + buffer reads done; a raw barrier, NOT __syncthreads(): its fence
-      // drains vmcnt and would cancel the PF - 1 tiles still in flight
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-  }
-
-  // ---- epilogue: stage fp32 tile of this wave in LDS, then coalesced 16-B stores ----
-  float* st = (float*)smem + wid * TM * (TN + 4);
-  constexpr int SLD = TN + 4;
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) st[(i * 16 + fg * 4 + q) * SLD + j * 16 + fr] = acc[i][j][q];
-  __syncthreads();
-
-  const int row0 = m0 + wm * TM, col0 = n0 + wn * TN;
-  if constexpr (EPI == EPI_SWIGLU) {
-    // output tile TM x TN/2; chunk of 8 outputs; TN/16 chunks per row
-    constexpr int CPR = TN / 16;
-    constexpr int RPI = 64 / CPR;
-    const int oc = (lane % CPR) * 8;          // output col within wave tile
-    const int grp = oc / 16, within = oc % 16;  // gate cols 32*grp+within.., up cols +16
-    const int ncols_out = p.N / 2;
-    const int gout = col0 / 2 + oc;
-    for (int rr = lane / CPR; rr < TM; rr += RPI) {
-      const int gm = row0 + rr;
-      if (gm >= p.M || gout >= ncols_out) continue;
-      const float* srow = st + rr * SLD + grp * 32 + within;
-      unsigned packed[4];
-#pragma unroll
-      for (int e = 0; e < 8; e += 2) {
-        float g0 = srow[e], g1 = srow[e + 1], u0 = srow[16 + e], u1 = srow[16 + e + 1];
-        packed[e / 2] = pack_bf2(silu(g0) * u0, silu(g1) * u1);
-      }
-      *(u32x4_t*)(p.C + (size_t)gm * p.ldc + gout) = u32x4_t{packed[0], packed[1], packed[2], packed[3]};
-    }
-  } else {
-    constexpr int CPR = TN / 8;
-    constexpr int RPI = 64 / CPR;
-    const int cc = (lane % CPR) * 8;
-    const int gn = col0 + cc;
-    for (int rr = lane / CPR; rr < TM; rr += RPI) {
-      const int gm = row0 + rr;
-      if (gm >= p.M || gn >= p.N) continue;
-      const float* srow = st + rr * SLD + cc;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = srow[e];
-      if constexpr (EPI == EPI_PARTIAL) {
-        float* dst = p.ws + ((size_t)blockIdx.z * p.M + gm) * p.N + gn;
-        *(f32x4_t*)dst = f32x4_t{v[0], v[1], v[2], v[3]};
-        *(f32x4_t*)(dst + 4) = f32x4_t{v[4], v[5], v[6], v[7]};
-        continue;
-      }
-      if (p.bias) {
-        u32x4_t b = *(const u32x4_t*)(p.bias + gn);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[2 * e] += bf2f((bf16_t)(b[e] & 0xffff));
-          v[2 * e + 1] += bf2f((bf16_t)(b[e] >> 16));
-        }
-      }
-      if constexpr (EPI == EPI_GELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
-      }
-      if constexpr (EPI == EPI_RESID) {
-        u32x4_t r = *(const u32x4_t*)(p.resid + (size_t)gm * p.ldr + gn);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[2 * e] += bf2f((bf16_t)(r[e] & 0xffff));
-          v[2 * e + 1] += bf2f((bf16_t)(r[e] >> 16));
-        }
-      }
-      *(u32x4_t*)(p.C + (size_t)gm * p.ldc + gn) =
-          u32x4_t{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-    }
-  }
+  constexpr bool W8 = false, W_NT = false;
+#include "gemm_tile_body.inc"
 }
 
 // Split-K reduction + epilogue. One thread per 8 output elements (16-B stores).
@@ -523,11 +326,25 @@ splitk_reduce_resid_rmsnorm(const float* __restrict__ ws, int splits, int M, int
   }
 }
 
-// C = resid + A.W^T (+ bias) and H = RMSNorm(C) * gamma in two launches (split-K GEMM + fused
-// reduce). M <= 64 (decode), N % 8 == 0, N <= 8192. ws holds splits * M * N floats.
-DA_EXPORT int da_gemm_resid_rmsnorm(const void* A, int lda, const void* W, void* C, int ldc, const void* bias,
-                                    const void* resid, int ldr, int M, int N, int K, int tile, int splits, void* ws,
-                                    const void* gamma, float eps, void* Hout, int ldh, void* stream) {
+// The e4m3 weight copy of the *_w8 entry points: codes [N, K] and fp32 row scales [N], both read 16 B
+// at a time.
+static bool w8_operands_ok(const void* Wq, const void* sw) {
+  return Wq && sw && (uintptr_t)Wq % 16 == 0 && (uintptr_t)sw % 16 == 0;
+}
+
+// The fp32 partials of a split-K launch on a weight-streaming decode tile: bf16 weights (a.W), or
+// with a.sw set the e4m3 codes a.W points at (gemm_tile_w8.hip: tiles 2 and 9, scaled partials).
+static int launch_partials(const GemmArgs& a, int tile, int splits, hipStream_t s) {
+  if (a.sw) return launch_gemm_tile_w8(a, tile, EPI_PARTIAL, splits, s);
+  return tile == 9   ? launch_tile<128, 64, 2, 2, 4>(a, EPI_PARTIAL, splits, s)
+         : tile == 2 ? launch_decode_tile<64, 128>(a, EPI_PARTIAL, splits, s)
+                     : launch_decode_tile<32, 128>(a, EPI_PARTIAL, splits, s);
+}
+
+// da_gemm_resid_rmsnorm / da_gemm_resid_rmsnorm_w8 (sw: the fp8 form, W = the codes)
+static int gemm_resid_rmsnorm(const void* A, int lda, const void* W, const float* sw, void* C, int ldc,
+                              const void* bias, const void* resid, int ldr, int M, int N, int K, int tile, int splits,
+                              void* ws, const void* gamma, float eps, void* Hout, int ldh, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (K % 64 || N % 8 || N > 8192 || lda % 8 || ldc % 8 || ldh % 8 || !ws || !gamma || !resid || !Hout)
     return (int)hipErrorInvalidValue;
@@ -535,17 +352,36 @@ DA_EXPORT int da_gemm_resid_rmsnorm(const void* A, int lda, const void* W, void*
   if (M == 0) return 0;
   GemmArgs a{};
   a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C;
-  a.bias = nullptr; a.resid = nullptr; a.ws = (float*)ws;
+  a.bias = nullptr; a.resid = nullptr; a.ws = (float*)ws; a.sw = sw;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.k_per_split = K / splits;
   // tile 9 (65..128 rows): one 128x64 weight-streaming tile per 64 weight rows
-  const int err = tile == 9   ? launch_tile<128, 64, 2, 2, 4>(a, EPI_PARTIAL, splits, s)
-                  : tile == 2 ? launch_decode_tile<64, 128>(a, EPI_PARTIAL, splits, s)
-                              : launch_decode_tile<32, 128>(a, EPI_PARTIAL, splits, s);
+  const int err = launch_partials(a, tile, splits, s);
   if (err) return err;
   splitk_reduce_resid_rmsnorm<<<M, 256, 0, s>>>((const float*)ws, splits, M, N, (const bf16_t*)bias,
                                                 (const bf16_t*)resid, ldr, (bf16_t*)C, ldc, (const bf16_t*)gamma, eps,
                                                 (bf16_t*)Hout, ldh);
   DA_LAUNCH_CHECK();
+}
+
+// C = resid + A.W^T (+ bias) and H = RMSNorm(C) * gamma in two launches (split-K GEMM + fused
+// reduce). M <= 128 (decode; above 64 rows tile 9 only), N % 8 == 0, N <= 8192. ws holds splits * M * N floats.
+DA_EXPORT int da_gemm_resid_rmsnorm(const void* A, int lda, const void* W, void* C, int ldc, const void* bias,
+                                    const void* resid, int ldr, int M, int N, int K, int tile, int splits, void* ws,
+                                    const void* gamma, float eps, void* Hout, int ldh, void* stream) {
+  return gemm_resid_rmsnorm(A, lda, W, nullptr, C, ldc, bias, resid, ldr, M, N, K, tile, splits, ws, gamma, eps, Hout,
+                            ldh, stream);
+}
+
+// da_gemm_resid_rmsnorm on W = Wq (e4m3 bytes [N, K]) times sw (fp32 [N]) per row: tile 2 (M <= 64) or
+// tile 9, 1 <= M <= 128; Wq and sw 16-B aligned.
+DA_EXPORT int da_gemm_resid_rmsnorm_w8(const void* A, int lda, const void* Wq, const void* sw, void* C, int ldc,
+                                       const void* bias, const void* resid, int ldr, int M, int N, int K, int tile,
+                                       int splits, void* ws, const void* gamma, float eps, void* Hout, int ldh,
+                                       void* stream) {
+  if (!w8_operands_ok(Wq, sw) || !A || !C || M < 1 || K < 64 || (tile != 2 && tile != 9) || (tile == 2 && M > 64))
+    return (int)hipErrorInvalidValue;
+  return gemm_resid_rmsnorm(A, lda, Wq, (const float*)sw, C, ldc, bias, resid, ldr, M, N, K, tile, splits, ws, gamma,
+                            eps, Hout, ldh, stream);
 }
 
 // Split-K reduce of a residual-producing decode GEMM (33..64 rows) in the gemm_dk layer structure:
@@ -583,10 +419,9 @@ splitk_reduce_resid_ssq(const float* __restrict__ ws, int splits, int M, int N, 
 // residual stream as A, the row scale applied in the reduce), or EPI_RESID with optional per-part
 // sums of squares out (ssq_out: [N / 512][64]). splits >= 2 whenever a reduce is needed; ws holds
 // splits * M * N floats.
-DA_EXPORT int da_gemm_dk_splitk(const void* A, int lda, const void* W, void* C, int ldc, const void* bias,
-                                const void* resid, int ldr, int M, int N, int K, int epi, const float* ssq_in,
-                                int ssq_parts, int norm_k, float eps, float* ssq_out, void* ws, int splits,
-                                void* stream) {
+static int gemm_dk_splitk(const void* A, int lda, const void* W, const float* sw, void* C, int ldc, const void* bias,
+                          const void* resid, int ldr, int M, int N, int K, int epi, const float* ssq_in,
+                          int ssq_parts, int norm_k, float eps, float* ssq_out, void* ws, int splits, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (M < 1 || M > 64 || K % 64 || N % 16 || lda % 8 || ldc % 8 || !ws || splits < 2 || (K / 64) % splits)
     return (int)hipErrorInvalidValue;
@@ -597,9 +432,9 @@ DA_EXPORT int da_gemm_dk_splitk(const void* A, int lda, const void* W, void* C, 
   if (epi != EPI_NONE && epi != EPI_BIAS && epi != EPI_SWIGLU && epi != EPI_RESID) return (int)hipErrorInvalidValue;
   GemmArgs a{};
   a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C;
-  a.ws = (float*)ws;
+  a.ws = (float*)ws; a.sw = sw;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.k_per_split = K / splits;
-  const int err = launch_decode_tile<64, 128>(a, EPI_PARTIAL, splits, s);
+  const int err = launch_partials(a, 2, splits, s);
   if (err) return err;
   if (epi == EPI_RESID && ssq_out) {
     splitk_reduce_resid_ssq<<<dim3(N / 512, M), 64, 0, s>>>((const float*)ws, splits, M, N, (const bf16_t*)bias,
@@ -613,6 +448,24 @@ DA_EXPORT int da_gemm_dk_splitk(const void* A, int lda, const void* W, void* C, 
                                              (const bf16_t*)resid, ldr, (bf16_t*)C, ldc, ssq_in, ssq_parts, norm_k,
                                              eps);
   DA_LAUNCH_CHECK();
+}
+
+DA_EXPORT int da_gemm_dk_splitk(const void* A, int lda, const void* W, void* C, int ldc, const void* bias,
+                                const void* resid, int ldr, int M, int N, int K, int epi, const float* ssq_in,
+                                int ssq_parts, int norm_k, float eps, float* ssq_out, void* ws, int splits,
+                                void* stream) {
+  return gemm_dk_splitk(A, lda, W, nullptr, C, ldc, bias, resid, ldr, M, N, K, epi, ssq_in, ssq_parts, norm_k, eps,
+                        ssq_out, ws, splits, stream);
+}
+
+// da_gemm_dk_splitk on W = Wq (e4m3 bytes [N, K]) times sw (fp32 [N]) per row; Wq and sw 16-B aligned.
+DA_EXPORT int da_gemm_dk_splitk_w8(const void* A, int lda, const void* Wq, const void* sw, void* C, int ldc,
+                                   const void* bias, const void* resid, int ldr, int M, int N, int K, int epi,
+                                   const float* ssq_in, int ssq_parts, int norm_k, float eps, float* ssq_out, void* ws,
+                                   int splits, void* stream) {
+  if (!w8_operands_ok(Wq, sw) || !A || !C || K < 64) return (int)hipErrorInvalidValue;
+  return gemm_dk_splitk(A, lda, Wq, (const float*)sw, C, ldc, bias, resid, ldr, M, N, K, epi, ssq_in, ssq_parts,
+                        norm_k, eps, ssq_out, ws, splits, stream);
 }
 
 // Prefill QKV projection with RoPE + KV-cache write fused into the epilogue (gemm8p EPI_ROPE);
@@ -675,5 +528,35 @@ DA_EXPORT int da_gemm_bf16(const void* A, int lda, const void* W, void* C, int l
   if (blocks > 4096) blocks = 4096;
   gemm_splitk_reduce<<<blocks, 256, 0, s>>>((const float*)ws, splits, M, N, epi, a.bias, a.resid, ldr,
                                              a.C, ldc);
+  DA_LAUNCH_CHECK();
+}
+
+// da_gemm_bf16's tiles 2 (64x128) and 9 (128x64) on W = Wq (e4m3 bytes [N, K]) times sw (fp32 [N]) per
+// row, 1 <= M <= 128: epi NONE / BIAS / SWIGLU / RESID, split-K through gemm_splitk_reduce. Wq and sw
+// 16-B aligned.
+DA_EXPORT int da_gemm_tile_w8(const void* A, int lda, const void* Wq, const void* sw, void* C, int ldc,
+                              const void* bias, const void* resid, int ldr, int M, int N, int K, int epi, int tile,
+                              int splits, void* ws, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!w8_operands_ok(Wq, sw) || !A || !C || M < 1 || M > 128 || K < 64 || (tile != 2 && tile != 9))
+    return (int)hipErrorInvalidValue;
+  if (K % 64 || N % 8 || lda % 8 || ldc % 8) return (int)hipErrorInvalidValue;
+  if (epi != EPI_NONE && epi != EPI_BIAS && epi != EPI_SWIGLU && epi != EPI_RESID) return (int)hipErrorInvalidValue;
+  if (epi == EPI_SWIGLU && N % 32) return (int)hipErrorInvalidValue;
+  if (epi == EPI_RESID && (!resid || ldr % 8)) return (int)hipErrorInvalidValue;
+  if (splits < 1) splits = 1;
+  if ((K / 64) % splits) return (int)hipErrorInvalidValue;
+  if (splits > 1 && ws == nullptr) return (int)hipErrorInvalidValue;
+  GemmArgs a{};
+  a.A = (const bf16_t*)A; a.W = (const bf16_t*)Wq; a.C = (bf16_t*)C; a.sw = (const float*)sw;
+  a.bias = (const bf16_t*)bias; a.resid = epi == EPI_RESID ? (const bf16_t*)resid : nullptr; a.ws = (float*)ws;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.k_per_split = K / splits;
+  const int err = launch_gemm_tile_w8(a, tile, epi, splits, s);
+  if (err || splits == 1) return err;
+  const int nout = (epi == EPI_SWIGLU) ? N / 2 : N;
+  const size_t work = (size_t)M * (nout / 8);
+  int blocks = (int)((work + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  gemm_splitk_reduce<<<blocks, 256, 0, s>>>((const float*)ws, splits, M, N, epi, a.bias, a.resid, ldr, a.C, ldc);
   DA_LAUNCH_CHECK();
 }

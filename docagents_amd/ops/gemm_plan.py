@@ -171,8 +171,8 @@ def plan_dk(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
     return GemmPlan("dk", TILE_DK, 1, 0)
 
 
-# gemm_dk on the decoder's e4m3 weight copy (csrc/gemm_dk_w8.hip): 2..32 rows only; 33..64 rows (the
-# split-K route) and everything wider stay on the bf16 tensors
+# gemm_dk on the decoder's e4m3 weight copy (csrc/gemm_dk_w8.hip): 2..32 rows only; 33..128 rows
+# stream the copy on the split-K tiles (tile_w8_fusable below)
 DK_W8_MAX_M = 32
 
 
@@ -188,6 +188,64 @@ def dk_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
 def plan_dk_w8(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
     """gemm_dk_w8()'s launch: always da_gemm_dk_w8, one launch, no split-K, no workspace."""
     return GemmPlan("dk_w8", TILE_DK, 1, 0)
+
+
+# The 64x128 / 128x64 weight-streaming tiles on the decoder's e4m3 weight copy (csrc/gemm_tile_w8.hip):
+# the 33..128-row decode steps, between gemm_dk_w8's rows and the prefill's
+TILE_W8_ABOVE = DK_W8_MAX_M
+TILE_W8_MAX_M = 128
+TILE_W8_SHORT_K_ROWS = 96  # 65..96 rows: products with K <= 3072 on the 128x64 tile stay on bf16 (tile_w8_fusable)
+
+
+def tile_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
+    """True when a decode step of M rows runs the product on the fp8 tile kernels (gemm_tile_w8,
+    gemm_dk_splitk_w8, gemm_resid_norm_w8) instead of the bf16 ones: every shape the kernels take at
+    33..128 rows. Which op runs it is the decoder body's choice; each launches the tile, split count
+    and workspace of the bf16 plan for the same (M, N, K, epi) (plan_tile_w8 / plan_dk_splitk_w8 /
+    plan_resid_norm_w8), so the step keeps its bits. Measurements: profiles/w8mid/README.md.
+
+    Held back:
+    * K = 64. The kernels take a single k-tile (and are tested on it), but such a product has no weight
+      stream to halve, and a decoder that narrow keeps no fp8 copy at all.
+    * 65..TILE_W8_SHORT_K_ROWS rows on the 128x64 tile (N < WIDE_N) with K <= 3072: Phi-3-mini's O
+      projection (3072 x 3072) at 96 rows ran 17.04 us against 16.95 us on bf16 (1.006x; the repeated
+      bf16 arm differed by 0.1 %), the one loss among the 20 (product, row count) pairs measured; it won
+      at 128 rows (0.984x) and the down projection (K = 8192) was level at 96 (0.999x). The 128x64 tile
+      re-reads the whole activation block per 64 weight rows, so there the weight bytes are not the bound."""
+    if _mid_rows(M) and M <= TILE_W8_SHORT_K_ROWS and N < WIDE_N and K <= 3072:
+        return False
+    return (TILE_W8_ABOVE < M <= TILE_W8_MAX_M and K >= 128 and K % 64 == 0 and N >= 8 and N % 8 == 0
+            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
+
+
+def _w8_tile(p: GemmPlan, what: str) -> GemmPlan:
+    if p.tile not in (TILE_64x128, TILE_128x64_PF4):
+        raise ValueError(f"{what}: the bf16 plan's tile {p.tile} has no fp8 form (tiles 2 and 9 only)")
+    return p
+
+
+def plan_tile_w8(M: int, N: int, K: int, epi: int = EPI_NONE, *, cus: int) -> GemmPlan:
+    """gemm_tile_w8()'s launch: what plan() gives gemm() for the same product. Where that is the
+    33..64-row split-K hand-off (plan_dk -> da_gemm_dk_splitk without norm or row sums) it is the
+    same launch by its tile name: 64x128 partials at dk_splits + gemm_splitk_reduce."""
+    p = plan(M, N, K, epi, cus=cus)
+    if p.family == "dk_splitk":
+        p = GemmPlan("tile", TILE_64x128, p.splits, p.ws_bytes)
+    return _w8_tile(p, "gemm_tile_w8")
+
+
+def plan_dk_splitk_w8(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
+    """gemm_dk_splitk_w8()'s launch: plan_dk's split-K route (33..64 rows; an ssq_out needs
+    N % 512 == 0, the reduce's part layout). ValueError where plan_dk runs the dk kernel itself."""
+    p = plan_dk(M, N, K, ssq_out)
+    if p.family != "dk_splitk":
+        raise ValueError(f"gemm_dk_splitk_w8: M={M} N={N} ssq_out={ssq_out} is not on the split-K route")
+    return p
+
+
+def plan_resid_norm_w8(M: int, N: int, K: int) -> GemmPlan:
+    """gemm_resid_norm_w8()'s launch: plan_resid_norm's (tile 2 at 33..64 rows, tile 9 above)."""
+    return _w8_tile(plan_resid_norm(M, N, K), "gemm_resid_norm_w8")
 
 
 # Prefill products on the fp8 256x256 tile (csrc/gemm256.hip, da_gemm_fp8; LLM_PREFILL_DTYPE=fp8):

@@ -19,7 +19,7 @@ import torch
 
 from . import gemm_plan
 from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: F401 - re-exported
-                        gemv_fusable, gemv_w8_fusable, prefill_w8_fusable)
+                        gemv_fusable, gemv_w8_fusable, prefill_w8_fusable, tile_w8_fusable)
 from .reference import quant_weight_fp8, quant_weight_fp8_pow2  # noqa: F401 - host-side torch, done once at load
 
 _LIB = None
@@ -73,6 +73,13 @@ _SIGS = {
                       c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "da_gemm_dk_splitk": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "da_gemm_tile_w8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                        c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "da_gemm_dk_splitk_w8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                             c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "da_gemm_resid_rmsnorm_w8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p],
+    "da_gemm_tile_w8_nt": [c_int],
     "da_decode_attn": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                        c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                        c_int, c_void_p],
@@ -471,6 +478,127 @@ def gemm_dk_w8(a, wq, sw, epi: int = EPI_NONE, bias=None, resid=None, out=None, 
                                _ptr(resid), ldr, M, N, K, epi, _ptr(ssq), parts, K, float(eps), _ptr(ssq_out),
                                _stream()), "gemm_dk_w8")
     return out
+
+
+def _w8_weights(name, wq, sw, K):
+    """The e4m3 weight copy of the 33..128-row ops: codes [N, K] and fp32 row scales [N], both read 16 B
+    at a time. Returns N."""
+    _req(wq.is_cuda and wq.dtype == FP8, f"wq must be float8_e4m3fn on GPU, got {wq.dtype}")
+    _req(wq.dim() == 2 and wq.is_contiguous() and wq.data_ptr() % 16 == 0, "wq must be contiguous, 16-B aligned")
+    _req(wq.shape[1] == K, f"{name}: K mismatch {K} vs {wq.shape[1]}")
+    N = wq.shape[0]
+    _req(sw.is_cuda and sw.dtype == torch.float32 and sw.is_contiguous() and sw.shape == (N,)
+         and sw.data_ptr() % 16 == 0, "sw must be fp32 [N], 16-B aligned")
+    return N
+
+
+def _tile_operands(name, a, N, epi, bias, resid, out):
+    """The operand checks of gemm_tile_w8 (gemm()'s, with every pointer 16-B aligned and the rows the
+    fp8 tiles take). Allocates ``out`` if None. Returns (M, K, out, ldr)."""
+    _bf16_cuda(a, "a")
+    _req(a.dim() == 2, f"{name} expects 2-D operands")
+    M, K = a.shape
+    _req(1 <= M <= gemm_plan.TILE_W8_MAX_M and K >= 64 and K % 64 == 0 and N >= 8 and N % 8 == 0,
+         f"{name} shape M={M} N={N} K={K}")
+    _req(epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0),
+         f"{name} does not take epi={epi} at N={N}")
+    _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.stride(0) >= K and a.data_ptr() % 16 == 0,
+         "a must be row-major, 16-B aligned rows")
+    nout = N // 2 if epi == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
+    _bf16_cuda(out, "out")
+    _req(out.shape == (M, nout) and out.stride(1) == 1 and out.stride(0) % 8 == 0 and out.stride(0) >= nout
+         and out.data_ptr() % 16 == 0, "bad out")
+    if bias is not None:
+        _bf16_cuda(bias, "bias")
+        _req(bias.numel() == N and bias.is_contiguous() and bias.data_ptr() % 16 == 0, "bias must be [N]")
+        _req(epi in (EPI_BIAS, EPI_RESID), "bias only with BIAS/RESID epilogues")
+    ldr = 0
+    if epi == EPI_RESID:
+        _req(resid is not None, "EPI_RESID needs resid")
+        _bf16_cuda(resid, "resid")
+        _req(resid.shape == (M, N) and resid.stride(1) == 1 and resid.stride(0) % 8 == 0 and resid.stride(0) >= N
+             and resid.data_ptr() % 16 == 0, "bad resid")
+        ldr = resid.stride(0)
+    return M, K, out, ldr
+
+
+def gemm_tile_w8(a, wq, sw, epi: int = EPI_NONE, bias=None, resid=None, out=None) -> torch.Tensor:
+    """gemm() at 1..128 rows on e4m3 weights with fp32 row scales, on the 64x128 / 128x64 weight-streaming
+    tiles: out = epi((a @ wq^T) * sw[None, :]), with the tile, split count and workspace gemm() takes
+    for the same product (gemm_plan.plan_tile_w8), so with power-of-two scales the result is gemm()'s
+    on the dequantised matrix bit for bit. Anything the kernel would refuse raises ValueError before
+    any launch (a product gemm() runs on another tile, e.g. at 32 rows or fewer, included)."""
+    _req(a.dim() == 2, "gemm_tile_w8 expects 2-D operands")
+    N = _w8_weights("gemm_tile_w8", wq, sw, a.shape[1])
+    M, K, out, ldr = _tile_operands("gemm_tile_w8", a, N, epi, bias, resid, out)
+    if epi != EPI_RESID:
+        resid = None
+    p = gemm_plan.plan_tile_w8(M, N, K, epi, cus=_cus(a.device))
+    ws = _workspace(p.ws_bytes, a.device) if p.ws_bytes else None
+    _check(lib().da_gemm_tile_w8(_ptr(a), a.stride(0), _ptr(wq), _ptr(sw), _ptr(out), out.stride(0), _ptr(bias),
+                                 _ptr(resid), ldr, M, N, K, epi, p.tile, p.splits, _ptr(ws), _stream()), "gemm_tile_w8")
+    return out
+
+
+def gemm_dk_splitk_w8(a, wq, sw, epi: int = EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
+    """gemm_dk's 33..64-row split-K route on e4m3 weights with fp32 row scales:
+    out = epi((rownorm(a) @ wq^T) * sw[None, :]), norm_in / ssq_out as gemm_dk (an ssq_out needs
+    N % 512 == 0: one part per 512 columns, dk_parts(N, M)). The split count and workspace are
+    plan_dk's. Anything the kernel would refuse raises ValueError before any launch."""
+    _req(a.dim() == 2, "gemm_dk_splitk_w8 expects 2-D operands")
+    N = _w8_weights("gemm_dk_splitk_w8", wq, sw, a.shape[1])
+    _req(DK_SPLITK_ABOVE < a.shape[0], f"gemm_dk_splitk_w8 takes {DK_SPLITK_ABOVE + 1}..{DK_MAX_M} rows, got {a.shape[0]}")
+    M, N, K, _, out, ldr, ssq, parts, eps = _dk_operands("gemm_dk_splitk_w8", a, N, DK_MAX_M, epi, bias, resid, out,
+                                                         norm_in, ssq_out)
+    _req(out.stride(0) >= out.shape[1] and (ldr == 0 or ldr >= N), "rows of out / resid overlap")
+    if epi != EPI_RESID:
+        resid = None
+    p = gemm_plan.plan_dk_splitk_w8(M, N, K, ssq_out is not None)
+    ws = _workspace(p.ws_bytes, a.device)
+    _check(lib().da_gemm_dk_splitk_w8(_ptr(a), a.stride(0), _ptr(wq), _ptr(sw), _ptr(out), out.stride(0), _ptr(bias),
+                                      _ptr(resid), ldr, M, N, K, epi, _ptr(ssq), parts, K, float(eps), _ptr(ssq_out),
+                                      _ptr(ws), p.splits, _stream()), "gemm_dk_splitk_w8")
+    return out
+
+
+def gemm_resid_norm_w8(a, wq, sw, resid, gamma, eps: float, out=None, h_out=None, bias=None):
+    """gemm_resid_norm at 33..128 rows on e4m3 weights with fp32 row scales: out = resid +
+    (a @ wq^T) * sw[None, :] (+ bias) and h_out = RMSNorm(out) * gamma, on plan_resid_norm's tile and
+    split count. Returns h_out. Anything the kernel would refuse raises ValueError before any launch."""
+    _bf16_cuda(a, "a"); _bf16_cuda(resid, "resid"); _bf16_cuda(gamma, "gamma")
+    _req(a.dim() == 2, "gemm_resid_norm_w8 expects 2-D operands")
+    M, K = a.shape
+    N = _w8_weights("gemm_resid_norm_w8", wq, sw, K)
+    _req(1 <= M <= gemm_plan.TILE_W8_MAX_M and K >= 64 and K % 64 == 0 and N >= 8 and N % 8 == 0 and N <= 8192,
+         f"gemm_resid_norm_w8 shape M={M} N={N} K={K}")
+    _req(a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.stride(0) >= K and a.data_ptr() % 16 == 0,
+         "a must be row-major, 16-B aligned rows")
+    _req(gamma.numel() == N and gamma.is_contiguous() and gamma.data_ptr() % 16 == 0 and eps > 0, "gamma must be [N], eps > 0")
+    out = resid if out is None else out
+    if h_out is None:
+        h_out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    for t, nm in ((resid, "resid"), (out, "out"), (h_out, "h_out")):
+        _bf16_cuda(t, nm)
+        _req(t.shape == (M, N) and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= N
+             and t.data_ptr() % 16 == 0, f"bad {nm}")
+    if bias is not None:
+        _bf16_cuda(bias, "bias")
+        _req(bias.numel() == N and bias.is_contiguous(), "bias must be [N]")
+    p = gemm_plan.plan_resid_norm_w8(M, N, K)
+    ws = _workspace(p.ws_bytes, a.device)
+    _check(lib().da_gemm_resid_rmsnorm_w8(_ptr(a), a.stride(0), _ptr(wq), _ptr(sw), _ptr(out), out.stride(0),
+                                          _ptr(bias), _ptr(resid), resid.stride(0), M, N, K, p.tile, p.splits, _ptr(ws),
+                                          _ptr(gamma), float(eps), _ptr(h_out), h_out.stride(0), _stream()),
+           "gemm_resid_norm_w8")
+    return h_out
+
+
+def gemm_tile_w8_nt(v: int = -1) -> int:
+    """The fp8 tiles' non-temporal code loads: 0 / 1 = every tile without / with, -1 = the per-tile
+    rule (csrc/gemm_tile_w8.hip); returns the setting. For A/B runs (bench/w8_mid.py)."""
+    return int(lib().da_gemm_tile_w8_nt(int(v)))
 
 
 def gemm_fp8(aq, sa, wq, sw, bias=None, epi: int = EPI_NONE, resid=None, out=None) -> torch.Tensor:

@@ -662,6 +662,28 @@ def gemm_resid_norm(a, w, resid, gamma, eps, out=None, h_out=None, bias=None):
     return h
 
 
+# The 33..128-row decode products on the e4m3 weight copy (csrc/gemm_tile_w8.hip): each is the bf16
+# form's reference op on the dequantised matrix wq * sw (held in fp32, as gemm_dk_w8 holds it). The
+# routing rule is the GPU's (pure Python), so the CPU decoder takes the same route.
+from .gemm_plan import tile_w8_fusable  # noqa: E402,F401
+
+
+def _dequant_w8(wq, sw):
+    return wq.float() * sw[:, None].float()
+
+
+def gemm_tile_w8(a, wq, sw, epi=EPI_NONE, bias=None, resid=None, out=None):
+    return gemm(a, _dequant_w8(wq, sw), bias=bias, epi=epi, resid=resid, out=out)
+
+
+def gemm_dk_splitk_w8(a, wq, sw, epi=EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
+    return gemm_dk(a, _dequant_w8(wq, sw), epi=epi, bias=bias, resid=resid, out=out, norm_in=norm_in, ssq_out=ssq_out)
+
+
+def gemm_resid_norm_w8(a, wq, sw, resid, gamma, eps, out=None, h_out=None, bias=None):
+    return gemm_resid_norm(a, _dequant_w8(wq, sw), resid, gamma, eps, out=out, h_out=h_out, bias=bias)
+
+
 # fp16 forms of the encoder ops (kernels.*_f16): these references keep the input dtype
 layernorm_f16 = layernorm
 bert_embed_ln_f16 = bert_embed_ln
