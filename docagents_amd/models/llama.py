@@ -22,6 +22,11 @@ them: rmsnorm_q8 (norm + per-token quantisation, no bf16 h) feeds QKV and gate/u
 and down, RoPE and the cache write are the separate rope_cache / rope_cache_kv8 launch. Attention,
 the residual stream, the LM head and every decode step are unchanged.
 
+weight_dtype="fp8": which products keep an e4m3 copy and which op a decode step calls on it is the
+planner's answer (ops.keeps_w8_copy, ops.weight_op: ops/gemm_plan.py); this module asks per product
+(``_product``). What it says itself is only which rows are a decode step's: in the plain body a single
+row is; wider rows there are a prefill pass's and stay on gemm() (or the W8A8 route above).
+
 TP layout (rank r of t): local q/k/v heads, F/t FFN features, vocab-parallel lm_head. Generation
 never gathers the [B, V/t] logits: each rank reduces its slice to 8 floats per row (best Gumbel
 score + its global index, local max, local sum-exp, the best's logit) and one tiny gather of those
@@ -31,6 +36,7 @@ in-place all-reduce yields x + sum of partials.
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
@@ -48,8 +54,7 @@ _FUSED_ROPE_DECODE = True
 # read (one per sequence); its K / V cache writes still cover every token (DA_PREFILL_TAIL=0: every
 # row through the whole layer; the tests compare both, bit for bit).
 _PREFILL_TAIL = os.environ.get("DA_PREFILL_TAIL", "1") != "0"
-_MID_W8_ANY_M = 64  # a row count inside ops.tile_w8_fusable's range: "at some 33..128-row decode step"
-_PF8_ANY_M = 1 << 20  # a row count above every row threshold of ops.prefill_w8_fusable: "at some prefill size"
+_BF16_OP = {"gemm": "gemm", "dk": "gemm_dk", "resid_norm": "gemm_resid_norm"}  # ops.weight_op's bodies
 
 
 class TPContext:
@@ -321,10 +326,9 @@ class LlamaDecoder:
         output row to e4m3 with a power-of-two scale and the bf16 tensor is replaced by the dequantised
         values (exact in bf16), so prefill and the wider decode steps compute the same model the batch-1
         fp8 GEMVs and the 2..128-row fp8 decode steps stream at half the bytes. The fp8 copy ({name}_q8
-        [N, K] e4m3, {name}_s8 [N] fp32) is kept only for the products ops.gemm_w8, ops.gemm_dk_w8 or the
-        33..128-row ops (ops.tile_w8_fusable) accept, and with prefill_dtype="fp8" for the layer products
-        ops.prefill_w8_fusable accepts (the LM head has at most 128 rows: never an fp8 prefill product);
-        the embedding and the norm gains stay bf16."""
+        [N, K] e4m3, {name}_s8 [N] fp32) is kept only where ops.keeps_w8_copy finds a row count that
+        streams it (the LM head has at most 128 rows: never an fp8 prefill product); the embedding and
+        the norm gains stay bf16."""
         o = self.ops
         pf8 = self.prefill_dtype == "fp8"
         prods = [(L, k, e) for L in self.w["layers"]
@@ -334,60 +338,31 @@ class LlamaDecoder:
             w = d[k]
             q, s = o.quant_weight_fp8_pow2(w)
             d[k] = (q.float() * s[:, None]).to(w.dtype).contiguous()
-            if (o.gemv_w8_fusable(1, w.shape[0], w.shape[1], epi) or o.dk_w8_fusable(2, w.shape[0], w.shape[1], epi)
-                    or o.tile_w8_fusable(_MID_W8_ANY_M, w.shape[0], w.shape[1], epi)
-                    or (pf8 and d is not self.w and o.prefill_w8_fusable(_PF8_ANY_M, w.shape[0], w.shape[1], epi))):
+            if o.keeps_w8_copy(w.shape[0], w.shape[1], epi, prefill_fp8=pf8 and d is not self.w):
                 d[k + "_q8"], d[k + "_s8"] = q, s
             del w, q, s
 
-    def _gemm1(self, d, name, a, **kw):
-        """The product a @ d[name]^T of a decode / prefill layer: the fp8 GEMV when ``a`` is one row
-        and the GEMV takes the weight's fp8 copy (weight_dtype="fp8"; a copy may be kept for gemm_dk_w8
-        alone, e.g. K = 256), today's bf16 ops.gemm otherwise."""
-        if self.weight_dtype == "fp8" and a.shape[0] == 1 and (name + "_q8") in d and self.ops.gemv_w8_fusable(
-                1, d[name].shape[0], d[name].shape[1], kw.get("epi", EPI_NONE)):
-            return self.ops.gemm_w8(a, d[name + "_q8"], d[name + "_s8"], **kw)
-        return self.ops.gemm(a, d[name], **kw)
+    def _product(self, body, d, name, a, **kw):
+        """The product a @ d[name]^T as a decode step of layer structure ``body`` runs it (ops.weight_op's
+        bodies; ``kw``: the op's keywords): the op ops.weight_op names, on the fp8 copy, where the weight
+        has one (weight_dtype="fp8"); the body's bf16 op on d[name] otherwise."""
+        w, op = d[name], _BF16_OP[body]
+        if self.weight_dtype == "fp8" and (name + "_q8") in d:
+            op = self.ops.weight_op(body, a.shape[0], w.shape[0], w.shape[1], kw.get("epi", EPI_NONE),
+                                    ssq_out=kw.get("ssq_out") is not None)
+        if op.endswith("_w8"):
+            return getattr(self.ops, op)(a, d[name + "_q8"], d[name + "_s8"], **kw)
+        return getattr(self.ops, op)(a, w, **kw)
 
-    def _dk_w8(self, d, name, B: int, epi: int) -> bool:
-        """True when the B-row gemm_dk product on d[name] streams the fp8 copy (ops.gemm_dk_w8)."""
-        w = d[name]
-        return (self.weight_dtype == "fp8" and (name + "_q8") in d
-                and self.ops.dk_w8_fusable(B, w.shape[0], w.shape[1], epi))
-
-    def _mid_w8(self, d, name, B: int, epi: int) -> bool:
-        """True when the product on d[name] of a 33..128-row decode step streams the fp8 copy
-        (ops.gemm_tile_w8 / gemm_dk_splitk_w8 / gemm_resid_norm_w8)."""
-        w = d[name]
-        return (self.weight_dtype == "fp8" and (name + "_q8") in d
-                and self.ops.tile_w8_fusable(B, w.shape[0], w.shape[1], epi))
-
-    def _gemm_dk1(self, d, name, a, epi: int = EPI_NONE, **kw):
-        """The product a @ d[name]^T of a gemm_dk decode layer on the fp8 copy where the weight has one
-        (weight_dtype="fp8"): gemm_dk_w8 at 2..32 rows, gemm_dk_splitk_w8 at 33..64 rows (the split-K
-        route; a producer of row sums is on it only with one part per 512 columns, as gemm_dk's is).
-        Today's ops.gemm_dk on the bf16 tensor otherwise."""
-        if self._dk_w8(d, name, a.shape[0], epi):
-            return self.ops.gemm_dk_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
-        if (self._mid_w8(d, name, a.shape[0], epi) and a.shape[0] <= self.ops.DK_MAX_M
-                and (kw.get("ssq_out") is None or d[name].shape[0] % 512 == 0)):
-            return self.ops.gemm_dk_splitk_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
-        return self.ops.gemm_dk(a, d[name], epi=epi, **kw)
-
-    def _gemm_mid1(self, d, name, a, epi: int = EPI_NONE, **kw):
-        """The product a @ d[name]^T of a fused-norm decode layer: gemm_tile_w8 on the fp8 copy at 33..128
-        rows where the weight has one (weight_dtype="fp8"), today's ops.gemm on the bf16 tensor otherwise."""
-        if self._mid_w8(d, name, a.shape[0], epi):
-            return self.ops.gemm_tile_w8(a, d[name + "_q8"], d[name + "_s8"], epi=epi, **kw)
-        return self.ops.gemm(a, d[name], epi=epi, **kw)
-
-    def _resid_norm_mid1(self, d, name, a, x, gamma, h_out):
-        """x += a @ d[name]^T and h_out = RMSNorm(x) * gamma of a fused-norm decode layer, on the fp8
-        copy at 33..128 rows as _gemm_mid1."""
-        if self._mid_w8(d, name, a.shape[0], EPI_RESID):
-            return self.ops.gemm_resid_norm_w8(a, d[name + "_q8"], d[name + "_s8"], x, gamma, self.cfg.eps, out=x,
-                                               h_out=h_out)
-        return self.ops.gemm_resid_norm(a, d[name], x, gamma, self.cfg.eps, out=x, h_out=h_out)
+    def _row_parallel(self, L, name, a, x, step: bool = False, **route):
+        """x += a @ L[name]^T of a row-parallel projection (O, down), before its all-reduce: rank 0's
+        epilogue adds the residual, the other ranks write their bare partial, so the sum over ranks is
+        x + every partial. ``step``: the rows are a decode step's (_product asks the planner for the
+        op); otherwise a prefill pass's, on gemm() with the caller's ``route`` keywords."""
+        res = dict(epi=EPI_RESID, resid=x) if self.tp.size == 1 or self.tp.rank == 0 else {}
+        if step:
+            return self._product("gemm", L, name, a, out=x, **res)
+        return self.ops.gemm(a, L[name], out=x, **res, **route)
 
     def _gain(self, g):
         """The gain a fused batch-1 GEMV norm streams: none once the gains are folded."""
@@ -400,26 +375,20 @@ class LlamaDecoder:
 
     # ------------------------------------------------------------- shared layer body
     def _attn_out_and_mlp(self, L, a, x):
-        o, tp = self.ops, self.tp
-        if tp.size == 1 or tp.rank == 0:
-            self._gemm1(L, "wo", a, epi=EPI_RESID, resid=x, out=x)
-        else:
-            o.gemm(a, L["wo"], out=x)
-        tp.all_reduce_(x)
+        # one row: a batch-1 step (or a one-token prefill, the same launches); wider rows are a prefill's
+        self._row_parallel(L, "wo", a, x, step=a.shape[0] == 1)
+        self.tp.all_reduce_(x)
         return self._mlp(L, x)
 
     def _mlp(self, L, x):
-        o, tp = self.ops, self.tp
+        o = self.ops
         if o.gemv_fusable(x.shape[0], L["w_gu"].shape[0], x.shape[1], EPI_SWIGLU):  # batch 1: norm fused
-            g = self._gemm1(L, "w_gu", x, epi=EPI_SWIGLU, rms=(self._gain(L["ln_mlp"]), self.cfg.eps))
+            g = self._product("gemm", L, "w_gu", x, epi=EPI_SWIGLU, rms=(self._gain(L["ln_mlp"]), self.cfg.eps))
         else:
             h = o.rmsnorm(x, L["ln_mlp"], self.cfg.eps)
             g = o.gemm(h, L["w_gu"], epi=EPI_SWIGLU)
-        if tp.size == 1 or tp.rank == 0:
-            self._gemm1(L, "w_down", g, epi=EPI_RESID, resid=x, out=x)
-        else:
-            o.gemm(g, L["w_down"], out=x)
-        tp.all_reduce_(x)
+        self._row_parallel(L, "w_down", g, x, step=x.shape[0] == 1)
+        self.tp.all_reduce_(x)
         return x
 
     def _tail_routes(self, M: int):
@@ -438,14 +407,12 @@ class LlamaDecoder:
         run the kernel (tile, K order, split count) the M-row pass would, so each row ends with the
         bits that pass gives it. The fused-norm GEMV that _mlp takes for a single row is not used."""
         o, tp = self.ops, self.tp
-        first = tp.size == 1 or tp.rank == 0  # the residual is added by one rank's epilogue only
-        res = dict(epi=EPI_RESID, resid=x) if first else {}
         r_o, r_gu, r_down = routes
-        o.gemm(a, L["wo"], out=x, **res, **r_o)
+        self._row_parallel(L, "wo", a, x, **r_o)
         tp.all_reduce_(x)
         h = o.rmsnorm(x, L["ln_mlp"], self.cfg.eps, route_m=M)
         g = o.gemm(h, L["w_gu"], epi=EPI_SWIGLU, **r_gu)
-        o.gemm(g, L["w_down"], out=x, **res, **r_down)
+        self._row_parallel(L, "w_down", g, x, **r_down)
         tp.all_reduce_(x)
         return x
 
@@ -509,8 +476,8 @@ class LlamaDecoder:
         ``out`` receives it)."""
         o = self.ops
         if o.gemv_fusable(hlast.shape[0], self.w["lm_head"].shape[0], hlast.shape[1]):
-            logits = self._gemm1(self.w, "lm_head", hlast.contiguous(), rms=(self._gain(self.w["norm"]), self.cfg.eps),
-                                 out=None if gather else out)
+            logits = self._product("gemm", self.w, "lm_head", hlast.contiguous(),
+                                   rms=(self._gain(self.w["norm"]), self.cfg.eps), out=None if gather else out)
         else:
             h = o.rmsnorm(hlast, self.w["norm"], self.cfg.eps)
             logits = o.gemm(h, self.w["lm_head"], out=None if gather else out)
@@ -523,6 +490,23 @@ class LlamaDecoder:
         over the xGMI peer buffers) -> the finalize kernel; every rank ends with the same token,
         logprob and bookkeeping, identical to sampling the gathered row."""
         return tp_sample(self.ops, self.tp, logits, temperature, seed, step, **kw)
+
+    def _sample_step(self, st: "DecodeState") -> torch.Tensor:
+        """The end of every decode step: sample st.logits into st.tokens with the state's bookkeeping."""
+        self.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
+                    active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
+        return st.tokens
+
+    def _prefix_kv(self, li: int, prefix):
+        """flash_attn_varlen's ``prefix`` for layer li: (k, v, P) of the shared P-token head in the
+        cache slot prefix[0], an fp8 cache's rows dequantised (exactly) to bf16; None without one."""
+        if prefix is None:
+            return None
+        slot, P = prefix
+        if self.kv_dtype == "fp8":
+            kq, vq, ks, vs = self.cache.kv8(li)
+            return self.ops.kv8_dequant(kq, ks, slot, P), self.ops.kv8_dequant(vq, vs, slot, P), P
+        return self.cache.k(li)[slot], self.cache.v(li)[slot], P
 
     # ------------------------------------------------------------- prefill
     def prefill(self, ids: torch.Tensor, pos: torch.Tensor, slot_tok: torch.Tensor, cu: torch.Tensor,
@@ -552,25 +536,14 @@ class LlamaDecoder:
             # attention reads its keys from the cache (Phi-3's D = 96), k / v go to the cache only
             if w8:
                 qkv = self._qkv_w8(L, li, x, pos, slot_tok)
-                if prefix is None:
-                    pre = None
-                elif kv8:
-                    kq, vq, ks, vs = cache.kv8(li)
-                    pre = (o.kv8_dequant(kq, ks, prefix[0], prefix[1]), o.kv8_dequant(vq, vs, prefix[0], prefix[1]),
-                           prefix[1])
-                else:
-                    pre = (cache.k(li)[prefix[0]], cache.v(li)[prefix[0]], prefix[1])
             elif kv8:
-                # the unfused path gemm_rope takes for short prefills, with the quantising cache write;
-                # the shared prefix is dequantised (exactly) to bf16 for the flash kernel, per layer
+                # the unfused path gemm_rope takes for short prefills, with the quantising cache write
                 kq, vq, ks, vs = cache.kv8(li)
                 qkv = o.rope_cache_kv8(o.gemm(h, L["wqkv"]), pos, self.cos_sin, hl, kl, D, slot_tok, kq, vq, ks, vs)
-                pre = None if prefix is None else (o.kv8_dequant(kq, ks, prefix[0], prefix[1]),
-                                                   o.kv8_dequant(vq, vs, prefix[0], prefix[1]), prefix[1])
             else:
                 qkv = o.gemm_rope(h, L["wqkv"], pos, self.cos_sin, hl, kl, D, slot_tok, cache.k(li), cache.v(li),
                                   kv_out=not kv_from_cache)
-                pre = None if prefix is None else (cache.k(li)[prefix[0]], cache.v(li)[prefix[0]], prefix[1])
+            pre = self._prefix_kv(li, prefix)  # (an fp8 cache's shared head: dequantised per layer)
             cut = tail is not None and li == last
             if kv_from_cache:
                 a = o.flash_attn_varlen(qkv[:, :hl * D], None, None, cu, max_seqlen, hl, kl, D, causal=True,
@@ -592,8 +565,7 @@ class LlamaDecoder:
 
     # ------------------------------------------------------------- decode (graph-capturable)
     def decode_step(self, st: "DecodeState") -> torch.Tensor:
-        c, o, cache = self.cfg, self.ops, self.cache
-        D, hl, kl = c.head_dim, self.hl, self.kl
+        c, o = self.cfg, self.ops
         x = o.embed(st.tokens, self.w["embed"], out=st.x)
         if self._dk_decode(x.shape[0]):
             return self._decode_step_dk(st, x)
@@ -604,7 +576,7 @@ class LlamaDecoder:
         fuse = o.gemv_fusable(x.shape[0], self.w["layers"][0]["wqkv"].shape[0], x.shape[1])
         for li, L in enumerate(self.w["layers"]):
             if fuse:  # batch 1: RMSNorm folded into the QKV GEMV (no separate norm launch)
-                qkv = self._gemm1(L, "wqkv", x, out=st.qkv, rms=(self._gain(L["ln_attn"]), c.eps))
+                qkv = self._product("gemm", L, "wqkv", x, out=st.qkv, rms=(self._gain(L["ln_attn"]), c.eps))
             else:
                 h = o.rmsnorm(x, L["ln_attn"], c.eps, out=st.h)
                 qkv = o.gemm(h, L["wqkv"], out=st.qkv)
@@ -613,9 +585,7 @@ class LlamaDecoder:
         logits = self._logits(x, gather=False, out=st.logits)  # straight into the state (no copy launch)
         if logits.data_ptr() != st.logits.data_ptr():
             st.logits.copy_(logits)
-        self.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
-                    active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
-        return st.tokens
+        return self._sample_step(st)
 
     def _decode_attn(self, qkv, li: int, st: "DecodeState"):
         """RoPE + new-token cache write + decode attention. MHA (Phi-3): one launch — the attention
@@ -661,7 +631,7 @@ class LlamaDecoder:
         c, o = self.cfg, self.ops
         layers = self.w["layers"]
         sa, sb = st.ssq
-        dk = self._gemm_dk1
+        dk = functools.partial(self._product, "dk")  # weight_dtype="fp8": the e4m3 copy where ops.weight_op says
         parts = o.dk_parts(c.hidden, x.shape[0])  # both kernels tile a residual producer alike: one part count
         a_in, norm = o.rmsnorm(x, layers[0]["ln_attn"], c.eps, out=st.h), None
         for li, L in enumerate(layers):
@@ -672,27 +642,23 @@ class LlamaDecoder:
             dk(L, "w_down", g, epi=EPI_RESID, resid=x, out=x, ssq_out=sb)                  # x += mlp
             a_in, norm = x, (sb, parts, c.eps)
         dk(self.w, "lm_head", x, out=st.logits, norm_in=norm)                             # final norm deferred
-        o.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
-                 active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
-        return st.tokens
+        return self._sample_step(st)
 
     def _decode_step_fused_norms(self, st: "DecodeState", x: torch.Tensor) -> torch.Tensor:
-        c, o, cache = self.cfg, self.ops, self.cache
-        D, hl, kl = c.head_dim, self.hl, self.kl
+        c, o = self.cfg, self.ops
         layers = self.w["layers"]
-        mm, rn = self._gemm_mid1, self._resid_norm_mid1  # 33..128 rows, weight_dtype="fp8": the e4m3 copy
+        mm = functools.partial(self._product, "gemm")  # weight_dtype="fp8": the e4m3 copy where ops.weight_op says
+        rn = functools.partial(self._product, "resid_norm", resid=x, eps=c.eps, out=x, h_out=st.h)
         h = o.rmsnorm(x, layers[0]["ln_attn"], c.eps, out=st.h)
         for li, L in enumerate(layers):
             qkv = mm(L, "wqkv", h, out=st.qkv)
             a = self._decode_attn(qkv, li, st)
-            h = rn(L, "wo", a, x, L["ln_mlp"], st.h)                                      # x += o; h = norm(x)
+            h = rn(L, "wo", a, gamma=L["ln_mlp"])                                         # x += o; h = norm(x)
             g = mm(L, "w_gu", h, epi=EPI_SWIGLU)
             nxt = layers[li + 1]["ln_attn"] if li + 1 < len(layers) else self.w["norm"]
-            h = rn(L, "w_down", g, x, nxt, st.h)                                          # x += mlp; h = norm(x)
+            h = rn(L, "w_down", g, gamma=nxt)                                             # x += mlp; h = norm(x)
         st.logits.copy_(mm(self.w, "lm_head", h))  # h already carries the final norm
-        o.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
-                 active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
-        return st.tokens
+        return self._sample_step(st)
 
     def _decode_step_tp_fused_norms(self, st: "DecodeState", x: torch.Tensor) -> torch.Tensor:
         """Tensor-parallel decode (B > 1) with the TP=1 fused-norm structure: every RMSNorm rides in
@@ -705,22 +671,14 @@ class LlamaDecoder:
         for li, L in enumerate(layers):
             qkv = o.gemm(h, L["wqkv"], out=st.qkv)
             a = self._decode_attn(qkv, li, st)
-            if tp.rank == 0:
-                o.gemm(a, L["wo"], epi=EPI_RESID, resid=x, out=x)
-            else:
-                o.gemm(a, L["wo"], out=x)
+            self._row_parallel(L, "wo", a, x)
             h = tp.all_reduce_norm_(x, L["ln_mlp"], c.eps, st.h, o)
             g = o.gemm(h, L["w_gu"], epi=EPI_SWIGLU)
-            if tp.rank == 0:
-                o.gemm(g, L["w_down"], epi=EPI_RESID, resid=x, out=x)
-            else:
-                o.gemm(g, L["w_down"], out=x)
+            self._row_parallel(L, "w_down", g, x)
             nxt = layers[li + 1]["ln_attn"] if li + 1 < len(layers) else self.w["norm"]
             h = tp.all_reduce_norm_(x, nxt, c.eps, st.h, o)
         st.logits.copy_(o.gemm(h, self.w["lm_head"]))  # h already carries the final norm; local vocab slice
-        self.sample(st.logits, st.temperature, st.seed, 0, out_tok=st.tokens, out_lp=st.lp, conf=st.conf,
-                    active=st.active, ctr=st.pos, pos=st.pos, lens=st.lens, hist=st.hist, start=st.start, eos=st.eos)
-        return st.tokens
+        return self._sample_step(st)
 
     def prefill_flops(self, lens) -> float:
         c = self.cfg

@@ -2,8 +2,10 @@
 library runs it, on which tile, with how many K splits and how much fp32 workspace.
 
 Pure Python (no torch, no ctypes): ``kernels.gemm`` / ``gemm_dk`` / ``gemm_resid_norm`` launch
-what ``plan`` / ``plan_dk`` / ``plan_resid_norm`` return, and nothing else decides.
-``tests/test_gemm_plan_cpu.py`` pins the table against ``tests/golden/gemm_routes.json``.
+what ``plan`` / ``plan_dk`` / ``plan_resid_norm`` return, the decoder calls the op ``weight_op``
+names and keeps the fp8 weight copies ``keeps_w8_copy`` asks for, and ``ops/reference.py`` (the CPU
+decoder) re-exports these objects: nothing else decides. ``tests/test_gemm_plan_cpu.py`` pins the
+tables against ``tests/golden/gemm_routes.json`` and ``tests/golden/w8_routes.json``.
 
 Tile ids (the ABI of ``da_gemm_bf16``'s ``switch``, csrc/gemm.hip): big tiles when the grid fills
 the CUs, skinny tiles (+ split-K) for decode-sized M.
@@ -54,16 +56,26 @@ def gemv_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     return M == 1 and K % 512 == 0 and N % 4 == 0 and (epi != EPI_SWIGLU or N % 32 == 0)
 
 
+def _decode_epi(N: int, epi: int) -> bool:
+    return epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0)
+
+
+def _gemv_w8_shape(N: int, K: int, epi: int) -> bool:
+    return K % 1024 == 0 and N % 4 == 0 and _decode_epi(N, epi)
+
+
 def gemv_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     """True when gemm_w8() accepts the product: the batch-1 GEMV on fp8 weights (csrc/gemv_w8.hip)."""
-    return (M == 1 and K % 1024 == 0 and N % 4 == 0 and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU)
-            and (epi != EPI_SWIGLU or N % 32 == 0))
+    return M == 1 and _gemv_w8_shape(N, K, epi)
+
+
+def _dk_shape(N: int, K: int, epi: int) -> bool:
+    return K % 256 == 0 and N % 16 == 0 and _decode_epi(N, epi)  # gemm_dk and gemm_dk_w8 alike
 
 
 def dk_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     """True when gemm() runs a decode-sized product on gemm_dk (no split-K)."""
-    return (DECODE_DK and 2 <= M <= DK_MAX_M and K % 256 == 0 and N % 16 == 0
-            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
+    return DECODE_DK and 2 <= M <= DK_MAX_M and _dk_shape(N, K, epi)
 
 
 def _mid_rows(M: int) -> bool:
@@ -181,8 +193,7 @@ def dk_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     shape the kernel takes at 2..32 rows (one row is the fp8 GEMV's, gemv_w8_fusable). fp8 beat the
     bf16 gemm_dk on all five Phi-3-mini products at 4, 16 and 32 rows (0.67-0.91x, profiles/w8dk/README.md),
     so no shape is held back. An EPI_RESID launch tiles like gemm_dk and writes dk_parts(N) parts."""
-    return (2 <= M <= DK_W8_MAX_M and K % 256 == 0 and N % 16 == 0
-            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
+    return 2 <= M <= DK_W8_MAX_M and _dk_shape(N, K, epi)
 
 
 def plan_dk_w8(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
@@ -195,6 +206,10 @@ def plan_dk_w8(M: int, N: int, K: int, ssq_out: bool = False) -> GemmPlan:
 TILE_W8_ABOVE = DK_W8_MAX_M
 TILE_W8_MAX_M = 128
 TILE_W8_SHORT_K_ROWS = 96  # 65..96 rows: products with K <= 3072 on the 128x64 tile stay on bf16 (tile_w8_fusable)
+
+
+def _tile_w8_shape(N: int, K: int, epi: int) -> bool:
+    return K >= 128 and K % 64 == 0 and N >= 8 and N % 8 == 0 and _decode_epi(N, epi)
 
 
 def tile_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
@@ -214,8 +229,7 @@ def tile_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
       re-reads the whole activation block per 64 weight rows, so there the weight bytes are not the bound."""
     if _mid_rows(M) and M <= TILE_W8_SHORT_K_ROWS and N < WIDE_N and K <= 3072:
         return False
-    return (TILE_W8_ABOVE < M <= TILE_W8_MAX_M and K >= 128 and K % 64 == 0 and N >= 8 and N % 8 == 0
-            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
+    return TILE_W8_ABOVE < M <= TILE_W8_MAX_M and _tile_w8_shape(N, K, epi)
 
 
 def _w8_tile(p: GemmPlan, what: str) -> GemmPlan:
@@ -254,6 +268,10 @@ def plan_resid_norm_w8(M: int, N: int, K: int) -> GemmPlan:
 PREFILL_W8_ABOVE = 128
 
 
+def _prefill_w8_shape(N: int, K: int, epi: int) -> bool:
+    return K % 128 == 0 and N % 8 == 0 and epi != EPI_BIAS and _decode_epi(N, epi)
+
+
 def prefill_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     """True when an fp8 prefill (prefill_dtype="fp8") runs the product of an M-row pass on
     da_gemm_fp8 instead of gemm(): every shape the kernel takes above the decode range. The rows a
@@ -267,11 +285,49 @@ def prefill_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     fill the 256 CUs once and whose K is at most 3072. There the tile's K loop is too short for the
     fp8 MFMA rate to pay for the pass: Phi-3's O projection in a batch-1 prefill (M = 2930, 144 tiles)
     ran 55.8 us against 55.2 us on the bf16 route; the down projection (same tiles, K = 8192) won."""
-    if not (M > PREFILL_W8_ABOVE and K % 128 == 0 and N % 8 == 0 and epi in (EPI_NONE, EPI_SWIGLU, EPI_RESID)
-            and (epi != EPI_SWIGLU or N % 32 == 0)):
+    if not (M > PREFILL_W8_ABOVE and _prefill_w8_shape(N, K, epi)):
         return False
     underfilled = -(-M // 256) * -(-N // 256) < 256
     return not (epi == EPI_RESID and M >= PREFILL_M and underfilled and K <= 3072)
+
+
+@functools.lru_cache(maxsize=4096)
+def weight_op(body: str, M: int, N: int, K: int, epi: int = EPI_NONE, *, ssq_out: bool = False) -> str:
+    """The name of the op a decoder calls for an M-row product on a weight that has an fp8 copy (the
+    bf16 op's name where the product stays on the bf16 tensor). ``body`` is the layer structure asking:
+
+    "gemm"        the plain / GEMV body, the fused-norm body's QKV, gate/up and LM head, the MLP and the
+                  logits: gemm_w8 at one row, gemm_tile_w8 at 33..128 rows, else gemm. One entry serves
+                  the one-row body and the fused-norm body: their fp8 row ranges are disjoint (1 against
+                  33..128), and a one-row step never takes the fused-norm body.
+    "dk"          the gemm_dk body: gemm_dk_w8 at 2..32 rows, gemm_dk_splitk_w8 where plan_dk puts the
+                  product on the split-K route (33..64 rows; with ssq_out only at N % 512 == 0, else the
+                  dk kernel writes the parts and gemm_dk_splitk_w8 would refuse), else gemm_dk.
+    "resid_norm"  the fused-norm body's O and down projections: gemm_resid_norm_w8 or gemm_resid_norm.
+
+    The W8A8 prefill is no entry here: it swaps the activation operand too (prefill_w8_fusable)."""
+    if body == "gemm":
+        if gemv_w8_fusable(M, N, K, epi):
+            return "gemm_w8"
+        return "gemm_tile_w8" if tile_w8_fusable(M, N, K, epi) else "gemm"
+    if body == "dk":
+        if dk_w8_fusable(M, N, K, epi):
+            return "gemm_dk_w8"
+        on_splitk = tile_w8_fusable(M, N, K, epi) and plan_dk(M, N, K, ssq_out).family == "dk_splitk"
+        return "gemm_dk_splitk_w8" if on_splitk else "gemm_dk"
+    if body == "resid_norm":
+        return "gemm_resid_norm_w8" if tile_w8_fusable(M, N, K, EPI_RESID) else "gemm_resid_norm"
+    raise ValueError(f"weight_op: unknown body {body!r}")
+
+
+def keeps_w8_copy(N: int, K: int, epi: int = EPI_NONE, *, prefill_fp8: bool = False) -> bool:
+    """True when some row count sends the [N, K] product to an op that streams the fp8 copy: the
+    shape conditions of gemv_w8_fusable (1 row), dk_w8_fusable (2..32), tile_w8_fusable (33..128) and,
+    for a decoder with an fp8 prefill, prefill_w8_fusable (above 128). What tile_w8_fusable and
+    prefill_w8_fusable hold back covers part of their row ranges only (65..96 rows; from PREFILL_M
+    rows while the tiles underfill the chip), so a shape they take is taken at some row count."""
+    return (_gemv_w8_shape(N, K, epi) or _dk_shape(N, K, epi) or _tile_w8_shape(N, K, epi)
+            or (prefill_fp8 and _prefill_w8_shape(N, K, epi)))
 
 
 def plan_resid_norm(M: int, N: int, K: int, tile: int = 0, splits: int = 0) -> GemmPlan:

@@ -19,7 +19,7 @@ import torch
 
 from . import gemm_plan
 from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: F401 - re-exported
-                        gemv_fusable, gemv_w8_fusable, prefill_w8_fusable, tile_w8_fusable)
+                        gemv_fusable, gemv_w8_fusable, keeps_w8_copy, prefill_w8_fusable, tile_w8_fusable, weight_op)
 from .reference import quant_weight_fp8, quant_weight_fp8_pow2  # noqa: F401 - host-side torch, done once at load
 
 _LIB = None

@@ -15,9 +15,10 @@ import torch.nn.functional as F
 EPI_NONE, EPI_BIAS, EPI_GELU, EPI_SWIGLU, EPI_RESID = 0, 1, 2, 3, 4
 EPI_ROPE = 6  # gemm8p only: QKV + RoPE + KV-cache write
 
-
-def gemv_fusable(M, N, K, epi=EPI_NONE):
-    return M == 1
+# No routing rule of its own: these ARE the planner's objects (pure Python), so a CPU decoder takes
+# the route the GPU one does. The DECODE_DK switch is read where it lives, gemm_plan.DECODE_DK.
+from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: E402,F401
+                        gemv_fusable, gemv_w8_fusable, keeps_w8_copy, prefill_w8_fusable, tile_w8_fusable, weight_op)
 
 
 def gemm_route(M, N, K, epi=EPI_NONE):
@@ -483,12 +484,6 @@ def rmsnorm_q8(x, g, eps, out=None, scale=None, route_m=0):
     return quant_fp8(rmsnorm(x, g, eps), out=out, scale=scale)
 
 
-def prefill_w8_fusable(M, N, K, epi=EPI_NONE):
-    """gemm_plan.prefill_w8_fusable: the CPU decoder runs the same W8A8 products the GPU one does."""
-    from .gemm_plan import prefill_w8_fusable as f
-    return f(M, N, K, epi)
-
-
 def quant_weight_fp8(w):
     """Per-output-channel e4m3 weight quantisation (host-side torch; done once at load)."""
     wf = w.float()
@@ -586,36 +581,11 @@ def kv8_dequant(codes, scale, slot, P):
     return kv8_dequant_all(codes[slot, :, :P], scale[slot, :, :P]).contiguous()
 
 
-def gemv_w8_fusable(M, N, K, epi=EPI_NONE):
-    return M == 1 and K % 1024 == 0
-
-
 def gemm_w8(a, wq, sw, bias=None, epi=EPI_NONE, resid=None, out=None, rms=None):
     if rms is not None:  # as gemm(): the bf16 normalised row
         g = rms[0] if rms[0] is not None else torch.ones(a.shape[1], dtype=a.dtype, device=a.device)
         a = rmsnorm(a, g, rms[1])
     return _epilogue((a.float() @ wq.float().t()) * sw[None, :].float(), wq.shape[0], bias, epi, resid, out)
-
-
-DECODE_DK = True
-# above 32 rows the split-K tiles stay faster (bench/midm_chain.py, profiles/r3/dk/): the narrow
-# dk tiles re-read the activation block once per 16-64 weight rows
-DK_MAX_M = 64
-DK_SPLITK_ABOVE = 32
-
-
-def dk_fusable(M, N, K, epi=EPI_NONE):
-    return (DECODE_DK and 2 <= M <= DK_MAX_M and K % 256 == 0 and N % 16 == 0
-            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
-
-
-def dk_parts(N, M=0):
-    """gemm_dk.hip dk_bn for EPI_RESID: row-norm partial sums written per output tile; 33..64 rows
-    (the split-K route): one per 512 columns (written by the reduce launch)."""
-    if DK_SPLITK_ABOVE < M <= 64 and N % 512 == 0:
-        return N // 512
-    bn = 64 if N // 64 >= 192 else (32 if N // 32 >= 192 else 16)
-    return (N + bn - 1) // bn
 
 
 def gemm_dk(a, w, epi=EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
@@ -638,11 +608,6 @@ def gemm_dk(a, w, epi=EPI_NONE, bias=None, resid=None, out=None, norm_in=None, s
     return y
 
 
-def dk_w8_fusable(M, N, K, epi=EPI_NONE):
-    return (2 <= M <= 32 and K % 256 == 0 and N % 16 == 0
-            and epi in (EPI_NONE, EPI_BIAS, EPI_RESID, EPI_SWIGLU) and (epi != EPI_SWIGLU or N % 32 == 0))
-
-
 def gemm_dk_w8(a, wq, sw, epi=EPI_NONE, bias=None, resid=None, out=None, norm_in=None, ssq_out=None):
     """gemm_dk_w8.hip: gemm_dk on the dequantised matrix wq * sw, held in fp32. With the decoder's
     power-of-two scales those values are exact in bf16 and this is bit for bit gemm_dk on the bf16
@@ -663,11 +628,7 @@ def gemm_resid_norm(a, w, resid, gamma, eps, out=None, h_out=None, bias=None):
 
 
 # The 33..128-row decode products on the e4m3 weight copy (csrc/gemm_tile_w8.hip): each is the bf16
-# form's reference op on the dequantised matrix wq * sw (held in fp32, as gemm_dk_w8 holds it). The
-# routing rule is the GPU's (pure Python), so the CPU decoder takes the same route.
-from .gemm_plan import tile_w8_fusable  # noqa: E402,F401
-
-
+# form's reference op on the dequantised matrix wq * sw (held in fp32, as gemm_dk_w8 holds it).
 def _dequant_w8(wq, sw):
     return wq.float() * sw[:, None].float()
 

@@ -121,10 +121,46 @@ def test_planner_imports_without_torch():
     assert r.returncode == 0, r.stderr
 
 
+def test_w8_routes_golden():
+    """weight_op / keeps_w8_copy against tests/golden/w8_routes.json, recorded at the parent of these
+    two functions by a throwaway script (the file's header says how): per (rows, product, ssq_out) the
+    op that commit's LlamaDecoder helpers called on a weight with an fp8 copy in each of the three layer
+    bodies, and per (product, fp8-prefill flag) whether its _quantise_weights_fp8 kept the copy."""
+    g = json.loads((Path(__file__).parent / "golden" / "w8_routes.json").read_text())
+    routes, copies = g["routes"], g["copies"]
+    assert len(routes) > 900 and len(copies) > 90
+    seen = {r[b] for r in routes for b in ("gemm", "dk", "resid_norm") if b in r}
+    assert seen == {"gemm", "gemm_w8", "gemm_tile_w8", "gemm_dk", "gemm_dk_w8", "gemm_dk_splitk_w8", "gemm_resid_norm",
+                    "gemm_resid_norm_w8"}
+    assert {c["keep"] for c in copies} == {True, False}
+    assert {r["M"] for r in routes} == {1, 2, 4, 16, 32, 33, 40, 64, 65, 96, 97, 128, 129, 640}
+    bad = []
+    for r in routes:
+        for body in ("gemm", "dk", "resid_norm"):
+            if body in r:
+                got = P.weight_op(body, r["M"], r["N"], r["K"], r["epi"], ssq_out=r["ssq_out"])
+                if got != r[body]:
+                    bad.append((body, r, got))
+    assert not bad, f"{len(bad)} routes differ, first: {bad[:3]}"
+    bad = [c for c in copies if P.keeps_w8_copy(c["N"], c["K"], c["epi"], prefill_fp8=c["prefill_fp8"]) != c["keep"]]
+    assert not bad, f"{len(bad)} of {len(copies)} copy answers differ, first: {bad[:3]}"
+    # the row sums of a 40-row O projection of width 256 come from the dk kernel itself (no part per 512 columns)
+    assert P.weight_op("dk", 40, 256, 256, P.EPI_RESID, ssq_out=True) == "gemm_dk"
+    assert P.weight_op("dk", 40, 256, 256, P.EPI_RESID) == "gemm_dk_splitk_w8"
+    with pytest.raises(ValueError):
+        P.weight_op("prefill", 640, 3072, 3072)
+
+
 def test_kernels_reexports_the_planners_objects():
     from docagents_amd.ops import kernels as K
+    from docagents_amd.ops import reference as R
     for name in ("gemv_fusable", "gemv_w8_fusable", "dk_fusable", "dk_parts"):
         assert getattr(K, name) is getattr(P, name)
+    for name in ("gemv_fusable", "gemv_w8_fusable", "dk_fusable", "dk_parts", "dk_w8_fusable", "tile_w8_fusable",
+                 "prefill_w8_fusable", "weight_op", "keeps_w8_copy"):
+        assert getattr(R, name) is getattr(P, name) and getattr(K, name) is getattr(P, name)
+    assert (R.DK_MAX_M, R.DK_SPLITK_ABOVE) == (P.DK_MAX_M, P.DK_SPLITK_ABOVE)
+    assert not hasattr(R, "DECODE_DK")  # one switch, the planner's: a copy here would go stale
     assert (K.DK_MAX_M, K.DK_SPLITK_ABOVE) == (P.DK_MAX_M, P.DK_SPLITK_ABOVE) == (64, 32)
     assert not any(hasattr(K, n) for n in ("_auto_splits", "_decode_tile", "_dk_splits", "_dk_splitk"))
     assert "da_gemm_route" not in K._SIGS
