@@ -262,10 +262,13 @@ class FlatIndex:
 
     # ----------------------------------------------------------------- search
     def _ranges_for(self, doc_filters):
+        """Per query: the row ranges of its documents (each document once, in the order first named:
+        the range scan walks the concatenated ranges, so a document named twice would be scanned, and
+        its rows returned, twice; ``= ANY(...)`` is a set) and the largest row total of any query."""
         ranges, off, maxrows = [], [0], 0
         for f in doc_filters:
             tot = 0
-            for d in (self.docs if f is None else f):  # None = every document
+            for d in (self.docs if f is None else dict.fromkeys(f)):  # None = every document
                 e = self.docs.get(d)
                 if e is None:
                     continue

@@ -73,10 +73,15 @@ class IVFFlatIndex(FlatIndex):
             self._build_lists()
             return True
 
-    def _assign(self, rows: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+    def _assign(self, rows: torch.Tensor, C: torch.Tensor, exact: bool = False) -> torch.Tensor:
         """Nearest centroid per row. Many rows x few centroids is a GEMM (rows . C^T on the MFMA
         GEMM kernel, 64k-row slices) + row argmax; the top-k scan kernel is built for the
-        opposite shape (few queries x many rows) and is only used for tiny inputs."""
+        opposite shape (few queries x many rows) and is only used for tiny inputs.
+
+        The GEMM writes bf16 scores: up to half an ulp (2^-8 for 1 <= |s| < 2) off each, so its argmax
+        can name a centroid that is not the nearest when two are close. The k-means iterations take
+        that; ``exact`` (the list build: a probe expects a row in its nearest centroid's list) sends
+        the rows whose two best rounded scores are within 2^-6 through the fp32 scan."""
         Cb = C.to(torch.bfloat16).contiguous()
         rows = rows.contiguous()
         if rows.shape[0] < 4096 or (rows.is_cuda and self.dim % 64):
@@ -84,14 +89,25 @@ class IVFFlatIndex(FlatIndex):
             return idx[:, 0].contiguous()
         out = torch.empty(rows.shape[0], dtype=torch.int32, device=rows.device)
         for a in range(0, rows.shape[0], 1 << 16):
-            s = self.ops.gemm(rows[a:a + (1 << 16)], Cb)
-            out[a:a + s.shape[0]] = torch.argmax(s, dim=1).int()
+            blk = rows[a:a + (1 << 16)]
+            s = self.ops.gemm(blk, Cb)
+            if not exact or Cb.shape[0] < 2:
+                out[a:a + s.shape[0]] = torch.argmax(s, dim=1).int()
+                continue
+            top = torch.topk(s.float(), 2, dim=1)
+            best = top.indices[:, 0].int()
+            near = torch.nonzero(top.values[:, 0] - top.values[:, 1] <= 2.0 ** -6).flatten()
+            if near.numel():
+                _, idx = self.ops.topk_dense(Cb, blk.index_select(0, near), 1, -2.0)
+                best[near] = idx[:, 0]
+            out[a:a + s.shape[0]] = best
         return out
 
     def _assign_chunked(self, X: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
+        """The list of every row of X under the trained centroids (exact: see _assign)."""
         out = torch.empty(X.shape[0], dtype=torch.int32, device=self.device)
         for a in range(0, X.shape[0], chunk):
-            out[a:a + chunk] = self._assign(X[a:a + chunk], self.centroids)
+            out[a:a + chunk] = self._assign(X[a:a + chunk], self.centroids, exact=True)
         return out
 
     def _build_lists(self):

@@ -365,7 +365,13 @@ topk_merge_kernel(float* __restrict__ cs, int* __restrict__ ci, int P, int Q, in
       const size_t o = ((size_t)pp * Q + q) * K + kk;
       const float v = cs[o];
       const int id = ci[o];
-      if (id >= 0 && better(v, id, bv, bi)) { bv = v; bi = id; bp = (int)o; }
+      // three selects on one flag: as `if (take) { bv = v; bi = id; bp = o; }` the tie path
+      // (v == bv, smaller id; also a real id under -inf against the empty start) kept the OLD bp
+      // in the generated code, so the round consumed the wrong candidate (or none)
+      const bool take = id >= 0 && better(v, id, bv, bi);
+      bv = take ? v : bv;
+      bi = take ? id : bi;
+      bp = take ? (int)o : bp;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -377,8 +383,12 @@ topk_merge_kernel(float* __restrict__ cs, int* __restrict__ ci, int P, int Q, in
     __syncthreads();
     if (tid == 0) {
       float fv = rv[0]; int fi = ri[0], fp = rp[0];
-      for (int w = 1; w < 4; ++w)
-        if ((ri[w] >= 0 && better(rv[w], ri[w], fv, fi)) || (fi < 0 && ri[w] >= 0)) { fv = rv[w]; fi = ri[w]; fp = rp[w]; }
+      for (int w = 1; w < 4; ++w) {
+        const bool take = (ri[w] >= 0 && better(rv[w], ri[w], fv, fi)) || (fi < 0 && ri[w] >= 0);
+        fv = take ? rv[w] : fv;
+        fi = take ? ri[w] : fi;
+        fp = take ? rp[w] : fp;
+      }
       os[(size_t)q * K + r] = fi >= 0 ? fv : -INFINITY;
       oi[(size_t)q * K + r] = fi;
       if (fp >= 0) ci[fp] = -1;  // consume

@@ -441,14 +441,16 @@ def topk_merge(cand_s, cand_i, K):
     P, Q, _ = cand_s.shape
     s = cand_s.permute(1, 0, 2).reshape(Q, -1)
     i = cand_i.permute(1, 0, 2).reshape(Q, -1)
-    s = torch.where(i < 0, torch.full_like(s, float("-inf")), s)
-    # sort by score desc, id asc
-    big = i.clamp_min(0).to(torch.float64)
-    key = s.to(torch.float64) * 1e12 - big
-    order = torch.argsort(key, dim=1, descending=True, stable=True)
-    vs, ii = torch.gather(s, 1, order)[:, :K], torch.gather(i, 1, order)[:, :K]
-    ii = torch.where(torch.isinf(vs), torch.full_like(ii, -1), ii)
-    return vs, ii
+    empty = i < 0
+    s = torch.where(empty, torch.full_like(s, float("-inf")), s)
+    i = torch.where(empty, torch.full_like(i, -1), i)
+    # lexicographic, as better() of csrc/vecsearch_topk.h: score desc, then id asc, empties (id < 0)
+    # last. Three stable sorts, least significant key first (a single mixed key such as
+    # score * 1e12 - id lets a large id difference outweigh a one-ulp score difference).
+    order = torch.argsort(i, dim=1, stable=True)
+    order = torch.gather(order, 1, torch.argsort(torch.gather(s, 1, order), dim=1, descending=True, stable=True))
+    order = torch.gather(order, 1, torch.argsort(torch.gather(empty, 1, order).to(torch.uint8), dim=1, stable=True))
+    return torch.gather(s, 1, order)[:, :K], torch.gather(i, 1, order)[:, :K]
 
 
 def kmeans_accum(X, assign, sums, counts):
