@@ -5,6 +5,7 @@ latency / QPS with and without a document filter, and IVF recall@k against the e
 
   python bench/index_bench.py --kind flat --rows 10000000 --dim 1024
   python bench/index_bench.py --kind ivfflat --rows 100000000 --dim 1024 --lists 8192 --probes 8,32
+  python bench/index_bench.py --kind ivfflat_fp8 --rows 10000000 --dim 1024 --lists 4096 --probes 16
 """
 from __future__ import annotations
 
@@ -51,7 +52,7 @@ def timeit(fn, reps=5):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="flat", choices=("flat", "ivfflat"))
+    ap.add_argument("--kind", default="flat", choices=("flat", "ivfflat", "ivfflat_fp8"))
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--chunk", type=int, default=1 << 21)
@@ -60,11 +61,11 @@ def main():
     ap.add_argument("--probes", default="8,32")
     ap.add_argument("--batches", default="1,64,512")
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8"), help="flat index row storage (INDEX_DTYPE)")
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8"), help="row storage (INDEX_DTYPE; --kind ivfflat --dtype fp8 is --kind ivfflat_fp8)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    if a.dtype == "fp8" and a.kind != "flat":
-        ap.error("--dtype fp8 needs --kind flat")
+    if a.kind == "ivfflat_fp8":
+        a.kind, a.dtype = "ivfflat", "fp8"
     dev = torch.device("cuda")
     gen, C = make_gen(a.dim, a.chunk, a.rows)
     nch = (a.rows + a.chunk - 1) // a.chunk
@@ -82,7 +83,7 @@ def main():
             ix.add_bulk([f"d{d}" for d in range(d0, d1 + 1)], per, np.arange(r0, r0 + x.shape[0]), x)
         del ndoc
     else:
-        ix = IVFFlatIndex(a.dim, dev, lists=a.lists, probes=1).build_streaming(
+        ix = IVFFlatIndex(a.dim, dev, lists=a.lists, probes=1, dtype=a.dtype).build_streaming(
             gen, a.rows, a.chunk, a.rows_per_doc, iters=8, sample=min(a.rows, 64 * a.lists))
     torch.cuda.synchronize()
     res["build_s"] = round(time.perf_counter() - t0, 2)

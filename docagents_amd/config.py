@@ -63,9 +63,12 @@ class Config:
     llm_prefill_dtype: str = field(default="bf16", metadata={"env": "LLM_PREFILL_DTYPE"})
     tp_size: int = field(default=1, metadata={"env": "TP_SIZE"})
     index_shards: int = field(default=1, metadata={"env": "INDEX_SHARDS"})
+    # flat (exact scan) | ivfflat (k-means lists over bf16 rows) | ivfflat_fp8 (the same index over fp8
+    # rows: e4m3 codes + one power-of-two fp32 scale per row, the storage of INDEX_DTYPE=fp8)
     index_kind: str = field(default="flat", metadata={"env": "INDEX_KIND"})
     # flat-index row storage: bf16, or fp8 = every row as e4m3 codes + one power-of-two fp32 scale
-    # (dim + 4 bytes per row instead of 2 dim): a capacity / bandwidth option (INDEX_KIND=flat only)
+    # (dim + 4 bytes per row instead of 2 dim): a capacity / bandwidth option (INDEX_KIND=flat; refused
+    # with ivfflat; ivfflat_fp8 names its own storage and takes either value)
     index_dtype: str = field(default="bf16", metadata={"env": "INDEX_DTYPE"})
     ivf_lists: int = field(default=100, metadata={"env": "IVF_LISTS"})
     ivf_probes: int = field(default=1, metadata={"env": "IVF_PROBES"})
@@ -154,14 +157,15 @@ class Config:
     KV_CACHE_DTYPES = ("bf16", "fp8")
     LLM_PREFILL_DTYPES = ("bf16", "fp8")
     INDEX_DTYPES = ("bf16", "fp8")
+    INDEX_KINDS = ("flat", "ivfflat", "ivfflat_fp8")
 
     def validate_engine(self) -> "Config":
         """Startup check of the engine keys whose wrong value would otherwise silently run a
         different configuration (the engine process calls it before touching the GPU)."""
         if self.dtype not in self.ENGINE_DTYPES:
             raise ValueError(f"DTYPE={self.dtype!r} is not supported (choose one of {', '.join(self.ENGINE_DTYPES)})")
-        if self.index_kind not in ("flat", "ivfflat"):
-            raise ValueError(f"INDEX_KIND={self.index_kind!r} is not supported (flat | ivfflat)")
+        if self.index_kind not in self.INDEX_KINDS:
+            raise ValueError(f"INDEX_KIND={self.index_kind!r} is not supported ({' | '.join(self.INDEX_KINDS)})")
         if self.tp_size < 1:
             raise ValueError(f"TP_SIZE={self.tp_size} must be >= 1")
         if self.llm_weight_dtype not in self.LLM_WEIGHT_DTYPES:
@@ -187,8 +191,9 @@ class Config:
         if self.index_dtype not in self.INDEX_DTYPES:
             raise ValueError(f"INDEX_DTYPE={self.index_dtype!r} is not supported "
                              f"(choose one of {', '.join(self.INDEX_DTYPES)})")
-        if self.index_dtype == "fp8" and self.index_kind != "flat":
-            # IVFFlat permutes and trains on the bf16 rows; there is no fp8 list store
+        if self.index_dtype == "fp8" and self.index_kind == "ivfflat":
+            # INDEX_DTYPE is the flat index's storage; fp8 IVFFlat lists are INDEX_KIND=ivfflat_fp8, which
+            # names its storage itself and takes either INDEX_DTYPE
             raise ValueError("INDEX_DTYPE=fp8 needs INDEX_KIND=flat")
         if self.search_transport not in ("plane", "rccl"):
             raise ValueError(f"SEARCH_TRANSPORT={self.search_transport!r} is not supported (plane | rccl)")

@@ -83,7 +83,8 @@ class Engine:
                                  seed=seed, eos=sorted(self.chat.eos_ids), use_graphs=use_graphs,
                                  share_prefix=share_prefix)
         from ..index import make_index
-        # index_dtype "fp8": flat-index rows as e4m3 codes + a scale per row (dim + 4 bytes instead of 2 dim)
+        # index_dtype "fp8": flat-index rows as e4m3 codes + a scale per row (dim + 4 bytes instead of 2 dim);
+        # index_kind "ivfflat_fp8": the IVFFlat index over the same fp8 rows (either index_dtype)
         self.index = make_index(index_kind, self.enc_cfg.hidden, self.device, lists=ivf_lists, probes=ivf_probes,
                                 dtype=index_dtype)
         self._prefix_cache: dict[str, list[int]] = {}

@@ -1,6 +1,14 @@
 """In-HBM vector indexes (flat brute force, IVFFlat) — the pgvector replacement."""
 from __future__ import annotations
 
+INDEX_KINDS = ("flat", "ivfflat", "ivfflat_fp8")
+
+
+def index_row_dtype(kind: str, dtype: str = "bf16") -> str:
+    """The row storage of an index of ``kind`` under INDEX_DTYPE=``dtype``: ivfflat_fp8 names its own
+    (fp8, whatever INDEX_DTYPE says); the other kinds store what INDEX_DTYPE says."""
+    return "fp8" if kind == "ivfflat_fp8" else dtype
+
 
 def make_index(kind: str, dim: int, device, lists: int = 100, probes: int = 1, capacity: int = 1024,
                dtype: str = "bf16"):
@@ -11,8 +19,11 @@ def make_index(kind: str, dim: int, device, lists: int = 100, probes: int = 1, c
         return FlatIndex(dim, device, capacity=capacity, dtype=dtype)
     if kind == "ivfflat":
         if dtype != "bf16":
-            # IVFFlat permutes and trains on the bf16 rows; an fp8 list store does not exist
+            # INDEX_DTYPE is the flat index's storage; the fp8 IVFFlat index is a kind of its own
             raise ValueError("INDEX_DTYPE=fp8 needs INDEX_KIND=flat")
         from .ivf import IVFFlatIndex
         return IVFFlatIndex(dim, device, lists=lists, probes=probes, capacity=capacity)
-    raise ValueError(f"unknown INDEX_KIND {kind!r} (flat | ivfflat)")
+    if kind == "ivfflat_fp8":
+        from .ivf import IVFFlatIndex
+        return IVFFlatIndex(dim, device, lists=lists, probes=probes, capacity=capacity, dtype="fp8")
+    raise ValueError(f"unknown INDEX_KIND {kind!r} ({' | '.join(INDEX_KINDS)})")

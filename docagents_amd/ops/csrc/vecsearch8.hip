@@ -1,5 +1,6 @@
-// fp8 (OCP e4m3) flat vector index: the row quantiser and the fp8 forms of the index scans of
-// vecsearch.hip (INDEX_DTYPE=fp8).
+// fp8 (OCP e4m3) vector index rows (INDEX_DTYPE=fp8, INDEX_KIND=ivfflat_fp8): the row quantiser (in
+// place and scattered), the row dequantiser and the k-means update over codes that IVFFlat training
+// uses, and the fp8 forms of the index scans of vecsearch.hip.
 //
 // Storage: a row of d values is d e4m3 codes plus ONE fp32 power-of-two scale: the smallest 2^e with
 // amax / 2^e <= 448 (1 for an all-zero row): fp8_pow2_scale (fp8.h). code * 2^e is exact in bf16.
@@ -14,16 +15,10 @@
 extern "C" int da_topk_merge(void* cand_s, void* cand_i, int P, int Q, int K, void* out_s, void* out_i, void* stream);
 
 // ------------------------------------------------------------------------------------------------
-// bf16 rows X [n, d] -> codes[(row0 + r) * d ..] and scale[row0 + r]. One wave per row (4 elements
-// per lane per step of 256), amax over the row by lane shuffles, then fp8_pow2_scale. Writes nothing
-// outside rows [row0, row0 + n).
-__global__ void __launch_bounds__(256)
-index_quant_rows_kernel(const bf16_t* __restrict__ X, int n, int d, uint8_t* __restrict__ codes,
-                        float* __restrict__ scale, long long row0) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;  // wave-uniform
-  const bf16_t* xr = X + (size_t)r * d;
+// One bf16 row xr[d] -> its codes cr[d] and its scale *sp, by one wave (4 elements per lane per step
+// of 256): amax over the row by lane shuffles, then fp8_pow2_scale.
+__device__ __forceinline__ void quant_row(const bf16_t* __restrict__ xr, int d, uint8_t* __restrict__ cr,
+                                          float* __restrict__ sp, int lane) {
   float amax = 0.f;
   for (int j = lane * 4; j < d; j += 256) {
     const u32x2_t a = *(const u32x2_t*)(xr + j);
@@ -33,12 +28,36 @@ index_quant_rows_kernel(const bf16_t* __restrict__ X, int n, int d, uint8_t* __r
   amax = wave_max(amax);
   float sc, inv;
   fp8_pow2_scale(amax, sc, inv);
-  uint8_t* cr = codes + ((size_t)row0 + r) * d;
   for (int j = lane * 4; j < d; j += 256) {
     const u32x2_t a = *(const u32x2_t*)(xr + j);
     *(unsigned*)(cr + j) = f32x4_fp8(bf2f(a[0] & 0xffff), bf2f(a[0] >> 16), bf2f(a[1] & 0xffff), bf2f(a[1] >> 16), inv);
   }
-  if (lane == 0) scale[row0 + r] = sc;
+  if (lane == 0) *sp = sc;
+}
+
+// bf16 rows X [n, d] -> codes[(row0 + r) * d ..] and scale[row0 + r]. One wave per row. Writes nothing
+// outside rows [row0, row0 + n).
+__global__ void __launch_bounds__(256)
+index_quant_rows_kernel(const bf16_t* __restrict__ X, int n, int d, uint8_t* __restrict__ codes,
+                        float* __restrict__ scale, long long row0) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;  // wave-uniform
+  quant_row(X + (size_t)r * d, d, codes + ((size_t)row0 + r) * d, scale + row0 + r, lane);
+}
+
+// The scatter form (the IVF streaming build): row r of X -> codes[dest[r]], scale[dest[r]], the rows of
+// dest distinct. A destination outside [0, cap) is skipped (the wrapper refuses it before the launch).
+__global__ void __launch_bounds__(256)
+index_quant_scatter_kernel(const bf16_t* __restrict__ X, int n, int d, uint8_t* __restrict__ codes,
+                           float* __restrict__ scale, const long long* __restrict__ dest, long long cap) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;  // wave-uniform
+  const long long t = dest[r];
+  DA_ASSERT(t >= 0 && t < cap);
+  if (t < 0 || t >= cap) return;  // wave-uniform
+  quant_row(X + (size_t)r * d, d, codes + (size_t)t * d, scale + t, lane);
 }
 
 DA_EXPORT int da_index_quant_rows(const void* X, int n, int d, void* codes, void* scale, long long row0,
@@ -47,6 +66,110 @@ DA_EXPORT int da_index_quant_rows(const void* X, int n, int d, void* codes, void
   if (n == 0) return 0;
   index_quant_rows_kernel<<<(n + 3) / 4, 256, 0, (hipStream_t)stream>>>((const bf16_t*)X, n, d, (uint8_t*)codes,
                                                                         (float*)scale, row0);
+  DA_LAUNCH_CHECK();
+}
+
+DA_EXPORT int da_index_quant_scatter(const void* X, int n, int d, void* codes, void* scale, const void* dest,
+                                     long long cap, void* stream) {
+  if (d % 4 || d < 4 || n < 0 || cap < 0 || !X || !codes || !scale || !dest) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  index_quant_scatter_kernel<<<(n + 3) / 4, 256, 0, (hipStream_t)stream>>>(
+      (const bf16_t*)X, n, d, (uint8_t*)codes, (float*)scale, (const long long*)dest, cap);
+  DA_LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------------------------------------
+// codes * scale -> bf16 (exact: fp8.h) for the IVF training paths: out[r] = row row0 + r of the store,
+// or row sel[r]. One wave per row, a 16-B piece of codes per lane per step of 1024 -> two 16-B stores.
+// d % 16 == 0. A source row outside [0, cap) is skipped (the wrapper refuses it before the launch).
+__global__ void __launch_bounds__(256)
+index_dequant_rows_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ scale, long long cap, int d,
+                          long long row0, const long long* __restrict__ sel, int n, bf16_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;  // wave-uniform
+  const long long t = sel ? sel[r] : row0 + r;
+  DA_ASSERT(t >= 0 && t < cap);
+  if (t < 0 || t >= cap) return;  // wave-uniform
+  const float sc = scale[t];
+  const uint8_t* cr = codes + (size_t)t * d;
+  bf16_t* orow = out + (size_t)r * d;
+  for (int j = lane * 16; j < d; j += 1024) {
+    const u32x4_t w = *(const u32x4_t*)(cr + j);
+    u32x4_t lo, hi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const f32x4_t f = fp8x4_f32(w[e]);
+      const unsigned p0 = pack_bf2(f[0] * sc, f[1] * sc), p1 = pack_bf2(f[2] * sc, f[3] * sc);
+      if (e < 2) { lo[2 * e] = p0; lo[2 * e + 1] = p1; } else { hi[2 * e - 4] = p0; hi[2 * e - 3] = p1; }
+    }
+    *(u32x4_t*)(orow + j) = lo;
+    *(u32x4_t*)(orow + j + 8) = hi;
+  }
+}
+
+DA_EXPORT int da_index_dequant_rows(const void* codes, const void* scale, long long cap, int d, long long row0,
+                                    const void* sel, int n, void* out, void* stream) {
+  if (d % 16 || d < 16 || n < 0 || cap < 0 || row0 < 0 || !codes || !scale || !out || ((uintptr_t)codes & 15) ||
+      ((uintptr_t)out & 15) || (!sel && row0 + n > cap))
+    return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  index_dequant_rows_kernel<<<(n + 3) / 4, 256, 0, (hipStream_t)stream>>>(
+      (const uint8_t*)codes, (const float*)scale, cap, d, row0, (const long long*)sel, n, (bf16_t*)out);
+  DA_LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------------------------------------
+// k-means update over fp8 rows (IVFFlat training on the codes): for every row with assign >= 0,
+// sums[assign] += scale[row] * code per element (exact in fp32: an e4m3 value times a power of two)
+// and counts[assign] += 1. One wave per row, 4 rows per workgroup. The row is read 16 B per lane
+// (1024 codes per step) and turned through LDS so that each atomic wave-instruction adds 64
+// neighbouring floats (256 contiguous bytes, the shape float atomics run fastest in); a lane takes the
+// dword of its code from LDS and converts the one byte. Rows with assign < 0 and lists that get no
+// row add nothing. d % 16 == 0.
+__global__ void __launch_bounds__(256)
+kmeans_accum8_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ scale, int N, int d,
+                     const int* __restrict__ assign, int L, float* __restrict__ sums, float* __restrict__ counts) {
+  __shared__ u32x4_t sW[4][64];  // per wave: 1024 codes of its row
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = blockIdx.x * 4 + wid;
+  int c = -1;
+  if (r < N) c = assign[r];
+  DA_ASSERT(c < L);
+  const bool on = c >= 0 && c < L;  // wave-uniform; every wave keeps the workgroup's barriers
+  const float sc = on ? scale[r] : 0.f;
+  const uint8_t* cr = codes + (size_t)(on ? r : 0) * d;
+  float* srow = sums + (size_t)(on ? c : 0) * d;
+  const unsigned* sD = (const unsigned*)sW[wid];
+  for (int base = 0; base < d; base += 1024) {
+    const int j = base + lane * 16;
+    u32x4_t w = u32x4_t{0, 0, 0, 0};
+    if (on && j < d) w = *(const u32x4_t*)(cr + j);
+    __syncthreads();  // the previous step's reads
+    sW[wid][lane] = w;
+    __syncthreads();
+    if (on) {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int e = base + t * 64 + lane;
+        if (e < d) {
+          const unsigned dw = sD[t * 16 + (lane >> 2)] >> ((lane & 3) * 8);
+          atomicAdd(&srow[e], __builtin_amdgcn_cvt_pk_f32_fp8(dw, false)[0] * sc);
+        }
+      }
+    }
+  }
+  if (on && lane == 0) atomicAdd(&counts[c], 1.f);
+}
+
+DA_EXPORT int da_kmeans_accum8(const void* codes, const void* scale, int N, int d, const void* assign, int L,
+                               void* sums, void* counts, void* stream) {
+  if (d % 16 || d < 16 || N < 0 || L < 1 || !codes || !scale || !assign || !sums || !counts ||
+      ((uintptr_t)codes & 15))
+    return (int)hipErrorInvalidValue;
+  if (N == 0) return 0;
+  kmeans_accum8_kernel<<<(N + 3) / 4, 256, 0, (hipStream_t)stream>>>(
+      (const uint8_t*)codes, (const float*)scale, N, d, (const int*)assign, L, (float*)sums, (float*)counts);
   DA_LAUNCH_CHECK();
 }
 

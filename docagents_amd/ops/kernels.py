@@ -95,6 +95,9 @@ _SIGS = {
                        c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "da_topk_merge": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "da_index_quant_rows": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p],
+    "da_index_quant_scatter": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
+    "da_index_dequant_rows": [c_void_p, c_void_p, c_longlong, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p],
+    "da_kmeans_accum8": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "da_topk_dense_stream8": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float,
                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "da_topk_ranges8": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
@@ -1253,18 +1256,58 @@ def _codes_cuda(codes, scale, rows: int):
     _req(codes.data_ptr() % 16 == 0, "codes alignment")
 
 
-def index_quant_rows(X, codes, scale, row0: int = 0):
+def _row_index(t, name: str, n: int, cap: int):
+    """An int64 [n] row list on the GPU with every entry inside [0, cap) (read back: one host sync)."""
+    _req(t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous() and t.numel() == n,
+         f"{name} must be contiguous int64 [{n}] on GPU")
+    if n:
+        lo, hi = torch.aminmax(t)
+        _req(int(lo) >= 0 and int(hi) < cap, f"{name} names rows outside [0, {cap})")
+
+
+def index_quant_rows(X, codes, scale, row0: int = 0, dest=None):
     """bf16 rows X [n, d] -> codes[row0:row0 + n] (uint8 / e4m3 [cap, d]) and scale[row0:row0 + n]
-    (fp32 [cap]), bit-identical to reference.quant_weight_fp8_pow2(X). Nothing else is written."""
+    (fp32 [cap]), bit-identical to reference.quant_weight_fp8_pow2(X). Nothing else is written.
+    ``dest`` (int64 [n], distinct rows inside codes; row0 must be 0): row r goes to codes[dest[r]],
+    scale[dest[r]] instead (the IVF streaming build's scatter pass)."""
     _bf16_cuda(X, "X")
     _req(X.dim() == 2 and X.is_contiguous() and X.data_ptr() % 8 == 0, "X must be contiguous [n, d]")
     n, d = X.shape
     row0 = int(row0)
+    if dest is not None:
+        _req(row0 == 0, "dest and row0 exclude each other")
+        _codes_cuda(codes, scale, codes.shape[0])
+        _req(d % 4 == 0 and codes.shape[1] == d, "d % 4 == 0 and codes [cap, d]")
+        _row_index(dest, "dest", n, codes.shape[0])
+        _check(lib().da_index_quant_scatter(_ptr(X), n, d, _ptr(codes), _ptr(scale), _ptr(dest), codes.shape[0],
+                                            _stream()), "index_quant_scatter")
+        return codes, scale
     _codes_cuda(codes, scale, row0 + n)
     _req(d % 4 == 0 and codes.shape[1] == d, "d % 4 == 0 and codes [cap, d]")
     _req(0 <= row0 and row0 + n <= codes.shape[0], "rows [row0, row0 + n) outside codes")
     _check(lib().da_index_quant_rows(_ptr(X), n, d, _ptr(codes), _ptr(scale), row0, _stream()), "index_quant_rows")
     return codes, scale
+
+
+def index_dequant_rows(codes, scale, out, row0: int = 0, sel=None):
+    """bf16 out [n, d] <- codes[r] * scale[r] (exact) for rows row0 .. row0 + n of the store, or for the
+    rows ``sel`` (int64 [n], repeats allowed; row0 must be 0): bit-identical to reference.index_dequant
+    of those rows. Nothing outside ``out`` is written."""
+    _bf16_cuda(out, "out")
+    _req(out.dim() == 2 and out.is_contiguous() and out.data_ptr() % 16 == 0, "out must be contiguous [n, d]")
+    n, d = out.shape
+    row0 = int(row0)
+    cap = codes.shape[0]
+    _codes_cuda(codes, scale, cap)
+    _req(d % 16 == 0 and d >= 16 and codes.shape[1] == d, "d % 16 == 0 and codes [cap, d]")
+    if sel is not None:
+        _req(row0 == 0, "sel and row0 exclude each other")
+        _row_index(sel, "sel", n, cap)
+    else:
+        _req(0 <= row0 and row0 + n <= cap, "rows [row0, row0 + n) outside codes")
+    _check(lib().da_index_dequant_rows(_ptr(codes), _ptr(scale), cap, d, row0, _ptr(sel), n, _ptr(out), _stream()),
+           "index_dequant_rows")
+    return out
 
 
 def _filter_args(N, Q, slots, bitmap):
@@ -1352,6 +1395,24 @@ def kmeans_accum(X, assign, sums, counts):
     N, d = X.shape
     _req(sums.dtype == torch.float32 and sums.shape[1] == d and counts.dtype == torch.float32, "sums/counts fp32")
     _check(lib().da_kmeans_accum(_ptr(X), N, d, _ptr(assign), _ptr(sums), _ptr(counts), _stream()), "kmeans_accum")
+
+
+def kmeans_accum8(codes, scale, assign, sums, counts):
+    """kmeans_accum over fp8 rows: sums[assign[r]] += codes[r] * scale[r] (exact terms), counts[assign[r]]
+    += 1 for every row with assign[r] >= 0. Rows with assign < 0 and lists that get no row change nothing."""
+    N, d = codes.shape
+    _codes_cuda(codes, scale, N)
+    _i32(assign, "assign")
+    _req(assign.numel() == N, "assign length")
+    _req(d % 16 == 0 and d >= 16, "d % 16 == 0")
+    _req(sums.is_cuda and sums.dtype == torch.float32 and sums.dim() == 2 and sums.is_contiguous()
+         and sums.shape[1] == d, "sums must be contiguous fp32 [L, d] on GPU")
+    L = sums.shape[0]
+    _req(counts.is_cuda and counts.dtype == torch.float32 and counts.is_contiguous() and counts.numel() == L,
+         "counts must be contiguous fp32 [L] on GPU")
+    _req(L >= 1, "no lists")
+    _check(lib().da_kmeans_accum8(_ptr(codes), _ptr(scale), N, d, _ptr(assign), L, _ptr(sums), _ptr(counts),
+                                  _stream()), "kmeans_accum8")
 
 
 def reserve_workspace(nbytes: int, device=None) -> None:

@@ -519,12 +519,42 @@ def index_dequant(codes, scale):
     return (c.float() * scale[:c.shape[0], None].float()).to(torch.bfloat16)
 
 
-def index_quant_rows(X, codes, scale, row0=0):
+def index_quant_rows(X, codes, scale, row0=0, dest=None):
+    """Rows [row0, row0 + n) of codes / scale <- quant_weight_fp8_pow2(X); with ``dest`` (int64 [n],
+    distinct rows) row r of X goes to row dest[r] instead."""
     n = X.shape[0]
     q, s = quant_weight_fp8_pow2(X.to(torch.bfloat16))
+    if dest is not None:
+        if row0 != 0:
+            raise ValueError("dest and row0 exclude each other")
+        if n and (int(dest.min()) < 0 or int(dest.max()) >= codes.shape[0]):
+            raise ValueError(f"dest names rows outside [0, {codes.shape[0]})")
+        codes.view(torch.uint8)[dest] = q.view(torch.uint8)
+        scale[dest] = s
+        return codes, scale
     codes.view(torch.uint8)[row0:row0 + n] = q.view(torch.uint8)
     scale[row0:row0 + n] = s
     return codes, scale
+
+
+def index_dequant_rows(codes, scale, out, row0=0, sel=None):
+    """out [n, d] bf16 <- index_dequant of rows row0 .. row0 + n, or of the rows ``sel`` (int64 [n])."""
+    n = out.shape[0]
+    if sel is not None:
+        if row0 != 0:
+            raise ValueError("sel and row0 exclude each other")
+        if n and (int(sel.min()) < 0 or int(sel.max()) >= codes.shape[0]):
+            raise ValueError(f"sel names rows outside [0, {codes.shape[0]})")
+        out.copy_(index_dequant(codes.index_select(0, sel), scale.index_select(0, sel)))
+    else:
+        if row0 < 0 or row0 + n > codes.shape[0]:
+            raise ValueError("rows [row0, row0 + n) outside codes")
+        out.copy_(index_dequant(codes[row0:row0 + n], scale[row0:row0 + n]))
+    return out
+
+
+def kmeans_accum8(codes, scale, assign, sums, counts):
+    kmeans_accum(index_dequant(codes, scale), assign, sums, counts)
 
 
 def topk_dense8(codes, scale, Qv, K, thr, slots=None, bitmap=None, **_):

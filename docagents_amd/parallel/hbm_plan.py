@@ -71,8 +71,11 @@ def encoder_bytes(cfg: EncoderConfig, enc_dtype: str = "bf16") -> int:
     return cfg.param_count() * 2 * (1 if enc_dtype == "bf16" else 2)
 
 
-def index_bytes(rows: int, dim: int, dtype: str = "bf16") -> int:
-    """The row (bf16, or INDEX_DTYPE=fp8: e4m3 codes + an fp32 scale) + int32 doc slot + int64 id."""
+def index_bytes(rows: int, dim: int, dtype: str = "bf16", kind: str = "flat") -> int:
+    """The row (bf16, or INDEX_DTYPE=fp8 / INDEX_KIND=ivfflat_fp8: e4m3 codes + an fp32 scale) + int32
+    doc slot + int64 id."""
+    from ..index import index_row_dtype
+    dtype = index_row_dtype(kind, dtype)
     if dtype not in ("bf16", "fp8"):
         raise ValueError(f"unknown index dtype {dtype!r} (bf16 | fp8)")
     return rows * ((dim + 4 if dtype == "fp8" else dim * 2) + 4 + 8)
