@@ -6,6 +6,7 @@
 #include "decode_merge.h"  // dec_chunk / dec_store / dec_finish / DecArgs / dec_fill / dec_combine
 
 #include <cstdlib>
+#include <type_traits>
 
 // Floating-point contraction only within one expression (a*b + c -> fma), never across statements:
 // with the HIP default (fast) the backend fuses differently depending on the code around an expression
@@ -92,7 +93,7 @@ decode_attn_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restri
   const size_t cbase = ((size_t)slot[b] * Hkv + hk) * (size_t)max_seq * D;
   const int P = pre ? pre[2 * b] : 0;  // shared-prefix keys [0, P) live in slot pre[2b + 1]
   const size_t pbase = P ? ((size_t)pre[2 * b + 1] * Hkv + hk) * (size_t)max_seq * D : cbase;
-  DA_ASSERT(P % 64 == 0 && P <= L);
+  DA_ASSERT(P >= 0 && P <= L);
   DA_ASSERT(!fr || rope.pos[b] == L - 1);
   __shared__ float skn[D], svn[D], ssn[G];
 
@@ -111,29 +112,39 @@ decode_attn_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restri
     return c + (t0 < P ? pbase : cbase) + (size_t)t0 * D;
   };
   // PFT loads are branch-free: a tile past kend reads key 0 of the row's own slot (one line, valid
-  // memory, never used) so the prefetches can be issued unconditionally
-  auto load_k = [&](u32x4_t (&kv)[CPR], int t0) {
+  // memory, never used) so the prefetches can be issued unconditionally.
+  // The tile that holds key P when P is no multiple of 64 takes its keys below P from the prefix slot
+  // and the others from the row's own: per-lane select in the PFT form (no branch around its loads),
+  // a wave-uniform branch otherwise, so that whole-tile prefixes run the loads they always ran.
+  auto load_kv = [&](const bf16_t* c, u32x4_t (&x)[CPR], int t0) {
     const int nk = kend - t0;
     const int last = min(KT, nk) * CPR - 1;
-    const bf16_t* kb = tile_base(kc, t0);
+    const bf16_t* tb = tile_base(c, t0);
+    const bf16_t* to = c + cbase + (size_t)t0 * D;                    // the same tile of the row's own slot
+    const bool str = t0 < P && P < t0 + KT;
+    const int cut = str ? (P - t0) * CPR : KT * CPR;                  // chunks below it: the tile's own source
+    if constexpr (PFT) {
 #pragma unroll
-    for (int i = 0; i < CPR; ++i) {
-      const int c = i * 64 + lane;
-      if constexpr (PFT) kv[i] = ld16(nk > 0 ? kb + min(c, last) * 8 : kc + cbase);
-      else kv[i] = (c <= last) ? ld16(kb + c * 8) : u32x4_t{0, 0, 0, 0};
+      for (int i = 0; i < CPR; ++i) {
+        const int cc = min(i * 64 + lane, last);
+        x[i] = ld16(nk > 0 ? (cc < cut ? tb : to) + cc * 8 : c + cbase);
+      }
+    } else if (str) {
+#pragma unroll
+      for (int i = 0; i < CPR; ++i) {
+        const int cc = i * 64 + lane;
+        x[i] = (cc <= last) ? ld16((cc < cut ? tb : to) + cc * 8) : u32x4_t{0, 0, 0, 0};
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < CPR; ++i) {
+        const int cc = i * 64 + lane;
+        x[i] = (cc <= last) ? ld16(tb + cc * 8) : u32x4_t{0, 0, 0, 0};
+      }
     }
   };
-  auto load_v = [&](u32x4_t (&vv)[CPR], int t0) {
-    const int nk = kend - t0;
-    const int last = min(KT, nk) * CPR - 1;
-    const bf16_t* vb = tile_base(vc, t0);
-#pragma unroll
-    for (int i = 0; i < CPR; ++i) {
-      const int c = i * 64 + lane;
-      if constexpr (PFT) vv[i] = ld16(nk > 0 ? vb + min(c, last) * 8 : vc + cbase);
-      else vv[i] = (c <= last) ? ld16(vb + c * 8) : u32x4_t{0, 0, 0, 0};
-    }
-  };
+  auto load_k = [&](u32x4_t (&kv)[CPR], int t0) { load_kv(kc, kv, t0); };
+  auto load_v = [&](u32x4_t (&vv)[CPR], int t0) { load_kv(vc, vv, t0); };
   // RoPE (interleaved pairs (2i, 2i+1)) of one element of a head row, rounded to bf16 like the
   // rope_cache kernel / the QKV GEMM epilogue that this path replaces
   constexpr int HALF = D / 2;
@@ -447,7 +458,7 @@ decode_attn_gqa_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __re
   const size_t cbase = ((size_t)slot[b] * Hkv + hk) * (size_t)max_seq * D;
   const int P = pre ? pre[2 * b] : 0;  // shared-prefix keys [0, P) live in slot pre[2b + 1]
   const size_t pbase = P ? ((size_t)pre[2 * b + 1] * Hkv + hk) * (size_t)max_seq * D : cbase;
-  DA_ASSERT(P % 64 == 0 && P <= L);
+  DA_ASSERT(P >= 0 && P <= L);
   char* myv = sv + w * VBYTES;
 
   bf16x8_t qf[NDS];
@@ -467,23 +478,35 @@ decode_attn_gqa_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __re
     const bf16_t* kb = kc + (shared ? pbase : cbase) + (size_t)t0 * D;
     const bf16_t* vb = vc + (shared ? pbase : cbase) + (size_t)t0 * D;
     // ---- K straight to registers (A operand rows = keys), then the V tile by LDS-DMA ----
+    // STR: the tile that holds key P when P is no multiple of 64 — its keys from P on come from the
+    // row's own slot (a wave-uniform branch: whole-tile prefixes run the loads they always ran)
     u32x4_t kr[4][NDS];
+    auto issue = [&](auto STR) {
+      constexpr bool S = decltype(STR)::value;
+      [[maybe_unused]] const int npre = P - t0;
+      [[maybe_unused]] const bf16_t* ko = kc + cbase + (size_t)t0 * D;
+      [[maybe_unused]] const bf16_t* vo = vc + cbase + (size_t)t0 * D;
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) {
-        const int key = min(16 * t + fr, nk - 1);
-        const u32x4_t* src = (const u32x4_t*)(kb + (size_t)key * D + ds * 32 + fg * 8);
-        kr[t][ds] = __builtin_nontemporal_load(src);
+        for (int ds = 0; ds < NDS; ++ds) {
+          const int key = min(16 * t + fr, nk - 1);
+          const bf16_t* base = (S && key >= npre) ? ko : kb;
+          const u32x4_t* src = (const u32x4_t*)(base + (size_t)key * D + ds * 32 + fg * 8);
+          kr[t][ds] = __builtin_nontemporal_load(src);
+        }
+#pragma unroll
+      for (int i = 0; i < NDMA; ++i) {
+        const int pc = i * 64 + lane, row = pc / NS, sl = pc % NS;
+        const int c = sl ^ vswz<D>(row);
+        const int key = min(row, nk - 1);
+        const bf16_t* base = (S && key >= npre) ? vo : vb;
+        // aux 2 = nt (read once per step; see decode_attn_mfma1_kernel)
+        __builtin_amdgcn_global_load_lds((gptr_t)(base + (size_t)key * D + c * 8), (lds_ptr_t)(myv + i * 1024), 16, 0, 2);
       }
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-      const int P = i * 64 + lane, row = P / NS, sl = P % NS;
-      const int c = sl ^ vswz<D>(row);
-      const int key = min(row, nk - 1);
-      // aux 2 = nt (read once per step; see decode_attn_mfma1_kernel)
-      __builtin_amdgcn_global_load_lds((gptr_t)(vb + (size_t)key * D + c * 8), (lds_ptr_t)(myv + i * 1024), 16, 0, 2);
-    }
+    };
+    if (shared && P < t0 + KT) issue(std::true_type{});
+    else issue(std::false_type{});
     // ---- S^T = K Q^T ----
     f32x4_t sacc[4];
 #pragma unroll
@@ -623,25 +646,32 @@ decode_attn_mfma1_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __
   const size_t cbase = ((size_t)slot[b] * Hkv + hk) * (size_t)max_seq * D;
   const int P = pre ? pre[2 * b] : 0;  // shared-prefix keys [0, P) live in slot pre[2b + 1]
   const size_t pbase = P ? ((size_t)pre[2 * b + 1] * Hkv + hk) * (size_t)max_seq * D : cbase;
-  DA_ASSERT(P % 64 == 0 && P <= L);
+  DA_ASSERT(P >= 0 && P <= L);
   DA_ASSERT(!RP || rope.pos[b] == L - 1);
 
   // ---- both tiles of this wave requested up front (branch-free: an empty tile reads key 0 of
   //      the row's own slot, valid memory whose scores are masked) ----
   const int ta = kstart + w * KT, tb = ta + 4 * KT;
   u32x4_t kr[2][4][NDS];
-  auto issue = [&](int j, int t0) {
+  // STR: the tile that holds key P when P is no multiple of 64 — its keys from P on come from the
+  // row's own slot (a wave-uniform branch in issue(): whole-tile prefixes run the loads they always ran)
+  auto issue_tile = [&](auto STR, int j, int t0) {
+    constexpr bool S = decltype(STR)::value;
     const int nk = kend - t0;
     const bool shared = t0 < P;
     const bf16_t* kb = nk > 0 ? kc + (shared ? pbase : cbase) + (size_t)t0 * D : kc + cbase;
     const bf16_t* vb = nk > 0 ? vc + (shared ? pbase : cbase) + (size_t)t0 * D : vc + cbase;
     const int last = nk > 0 ? min(KT, nk) - 1 : 0;
+    [[maybe_unused]] const int npre = P - t0;  // S: nk > 0 (issue() checks), so kb / vb are the prefix slot's tile
+    [[maybe_unused]] const bf16_t* ko = kc + cbase + (size_t)t0 * D;
+    [[maybe_unused]] const bf16_t* vo = vc + cbase + (size_t)t0 * D;
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int ds = 0; ds < NDS; ++ds) {
         const int key = min(16 * t + fr, last);
-        kr[j][t][ds] = __builtin_nontemporal_load((const u32x4_t*)(kb + (size_t)key * D + ds * 32 + fg * 8));
+        const bf16_t* base = (S && key >= npre) ? ko : kb;
+        kr[j][t][ds] = __builtin_nontemporal_load((const u32x4_t*)(base + (size_t)key * D + ds * 32 + fg * 8));
       }
     char* myv = sv + (w * 2 + j) * VBYTES;
 #pragma unroll
@@ -649,10 +679,15 @@ decode_attn_mfma1_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __
       const int pc = i * 64 + lane, row = pc / NS, sl = pc % NS;
       const int c = sl ^ vswz1<D>(row);
       const int key = min(row, last);
+      const bf16_t* base = (S && key >= npre) ? vo : vb;
       // aux 2 = nt: the KV stream is read once per step; allocating it in L2 / MALL cost the GEMVs
       // that follow ~3 % (their weights lose cache residency): profiles/r5/decode_mfma1/
-      __builtin_amdgcn_global_load_lds((gptr_t)(vb + (size_t)key * D + c * 8), (lds_ptr_t)(myv + i * 1024), 16, 0, 2);
+      __builtin_amdgcn_global_load_lds((gptr_t)(base + (size_t)key * D + c * 8), (lds_ptr_t)(myv + i * 1024), 16, 0, 2);
     }
+  };
+  auto issue = [&](int j, int t0) {
+    if (t0 < P && P < t0 + KT && t0 < kend) issue_tile(std::true_type{}, j, t0);
+    else issue_tile(std::false_type{}, j, t0);
   };
   issue(0, ta);
   issue(1, tb);

@@ -158,7 +158,7 @@ decode_attn_kv8_kernel(const bf16_t* __restrict__ q, int ldq, const uint8_t* __r
   const size_t crow = ((size_t)slot[b] * Hkv + hk) * (size_t)max_seq;  // first cache row of (slot, kv head)
   const int P = pre ? pre[2 * b] : 0;  // shared-prefix keys [0, P) live in slot pre[2b + 1]
   const size_t prow = P ? ((size_t)pre[2 * b + 1] * Hkv + hk) * (size_t)max_seq : crow;
-  DA_ASSERT(P % 64 == 0 && P <= L);
+  DA_ASSERT(P >= 0 && P <= L);
 
   auto ld16 = [&](const uint8_t* p) -> u32x4_t { return __builtin_nontemporal_load((const u32x4_t*)p); };
   // branch-free per lane: chunks / keys past the tile's end read nothing and are zero (code 0 = 0.0)
@@ -168,6 +168,22 @@ decode_attn_kv8_kernel(const bf16_t* __restrict__ q, int ldq, const uint8_t* __r
     const size_t r0 = (t0 < P ? prow : crow) + (size_t)t0;
     const uint8_t* kb = kc + r0 * D;
     const uint8_t* vb = vc + r0 * D;
+    if (t0 < P && P < t0 + KT) {
+      // the tile that holds key P when P is no multiple of 64: its keys from P on come from the row's
+      // own slot (a wave-uniform branch: whole-tile prefixes run the loads below, as they always did)
+      const size_t o0 = crow + (size_t)t0;
+      const int npre = P - t0, cut = npre * CPR;
+#pragma unroll
+      for (int i = 0; i < CPR; ++i) {
+        const int c = i * 64 + lane;
+        kv[i] = (c <= last) ? ld16(kc + (c < cut ? r0 : o0) * D + c * 16) : u32x4_t{0, 0, 0, 0};
+        vv[i] = (c <= last) ? ld16(vc + (c < cut ? r0 : o0) * D + c * 16) : u32x4_t{0, 0, 0, 0};
+      }
+      const size_t rs = (lane < npre ? r0 : o0) + lane;
+      ks = lane < nk ? __builtin_nontemporal_load(ksc + rs) : 0.f;
+      vs = lane < nk ? __builtin_nontemporal_load(vsc + rs) : 0.f;
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < CPR; ++i) {
       const int c = i * 64 + lane;

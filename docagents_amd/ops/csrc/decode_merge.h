@@ -136,8 +136,8 @@ struct DecArgs {
 // caller's to check. 0, or hipErrorInvalidValue: refused. B == 0 passes (nothing to launch).
 // ws must hold B*H*nsplit*(D+2) floats. chunk = keys per split (multiple of 64).
 // pre (nullable): int32 [B][2] = (P, prefix slot) per row — keys [0, P) of row b are read from the
-// prefix slot (a prompt head shared by the whole batch, stored once; P % 64 == 0 so no 64-key tile
-// straddles the two sources). Every row of the batch reads the same prefix lines, so they are served
+// prefix slot (a prompt head shared by the whole batch, stored once; the decoder passes whole 64-key
+// tiles, and the one tile that straddles the two sources at any other P selects its source per key). Every row of the batch reads the same prefix lines, so they are served
 // from L2 / MALL instead of HBM.
 // counters (nullable): int32 [B * Hkv], all zero, left zero by every launch -> the splits are merged
 // inside the attention kernel (last split per (b, kv head)); null -> separate combine launch. With

@@ -990,8 +990,9 @@ def decode_attn(q, k_cache, v_cache, lens, slot, H, Hkv, D, max_len: int, chunk:
     """q [B, >=H*D] (row stride any multiple of 8); lens/slot int32 [B]; max_len = max(lens) or the
     cache capacity (host int, fixes the split count so the launch is graph-capturable).
     chunk = keys per workgroup (0 = auto: enough workgroups to fill 256 CUs, 4 waves x 64-key tiles).
-    pre: optional int32 [B, 2] device tensor (P, prefix slot), P % 64 == 0: keys [0, P) of row b
-    are the batch's shared prompt head, stored once in the prefix slot (read through the cache).
+    pre: optional int32 [B, 2] device tensor (P, prefix slot), 0 <= P <= lens: keys [0, P) of row b
+    are the batch's shared prompt head, stored once in the prefix slot (read through the cache; any P,
+    whole 64-key tiles being the form the decoder uses).
     rope = (cos_sin fp32 [max_pos, D/2, 2], pos int32 [B]), MHA only: q is the raw qkv row
     [B, (H + 2 Hkv) D]; the kernel applies RoPE to q and the new token's k and writes that token's
     k / v into the cache at pos (== lens - 1) — the decode step's rope_cache launch folded in."""
@@ -1043,7 +1044,7 @@ def decode_attn_kv8(q, k_codes, v_codes, k_scale, v_scale, lens, slot, H, Hkv, D
                     scale=None, out=None, pre=None):
     """decode_attn (without rope=) over the fp8 cache: q [B, >= H*D] bf16 (any row stride), lens / slot
     int32 [B], max_len fixes the split count (graph-capturable), pre int32 [B, 2] = (P, prefix slot)
-    with P % 64 == 0, out bf16 with any row stride. Splits merge in the kernel through the uncached
+    with 0 <= P <= lens, out bf16 with any row stride. Splits merge in the kernel through the uncached
     workspace and ticket (or a combine launch with _FUSED_COMBINE off); never the same-XCD exchange."""
     _kv8_cache_checks(k_codes, v_codes, k_scale, v_scale, Hkv, D)
     chunk, nsplit, out, _, _ = _decode_operands(q, lens, slot, H, Hkv, D, max_len, k_codes.shape[2], chunk, out, pre)
