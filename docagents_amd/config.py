@@ -52,7 +52,9 @@ class Config:
     embed_dim: int = field(default=0, metadata={"env": "EMBED_DIM"})  # 0 -> encoder hidden size
     dtype: str = field(default="bf16", metadata={"env": "DTYPE"})
     # decoder weight storage: bf16, or fp8 = the decoder quantised per output row to OCP e4m3 with an
-    # e4m3 copy of every matmul weight that the batch-1 decode GEMVs stream (TP_SIZE=1 only)
+    # e4m3 copy of every matmul weight that the batch-1 decode GEMVs stream (TP_SIZE=1 only), or mxfp4 = the
+    # decoder quantised to OCP MXFP4 (e2m1 codes + one e8m0 scale per 32 k) with a copy of the codes that the
+    # batch-1 decode GEMVs stream; steps of 2+ rows and prefill run bf16 on the dequantised tensors (TP_SIZE=1 only)
     llm_weight_dtype: str = field(default="bf16", metadata={"env": "LLM_WEIGHT_DTYPE"})
     # decoder KV-cache storage: bf16, or fp8 = every cached K / V row as e4m3 codes + one power-of-two
     # fp32 scale (D + 4 bytes per row instead of 2 D): a throughput / capacity option (TP_SIZE=1 only)
@@ -153,7 +155,7 @@ class Config:
     # (f16 MFMA GEMMs + flash, fp16 LayerNorm: BASELINE config 4); fp8 (OCP e4m3) encoder GEMMs.
     # Anything else is refused at startup, never run as something else.
     ENGINE_DTYPES = ("bf16", "fp16", "fp8")
-    LLM_WEIGHT_DTYPES = ("bf16", "fp8")
+    LLM_WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
     KV_CACHE_DTYPES = ("bf16", "fp8")
     LLM_PREFILL_DTYPES = ("bf16", "fp8")
     INDEX_DTYPES = ("bf16", "fp8")
@@ -182,6 +184,8 @@ class Config:
         if self.llm_weight_dtype == "fp8" and self.tp_size > 1:
             # quantising per TP shard is a different model from quantising the whole
             raise ValueError("LLM_WEIGHT_DTYPE=fp8 needs TP_SIZE=1")
+        if self.llm_weight_dtype == "mxfp4" and self.tp_size > 1:
+            raise ValueError("LLM_WEIGHT_DTYPE=mxfp4 needs TP_SIZE=1")
         if self.kv_cache_dtype not in self.KV_CACHE_DTYPES:
             raise ValueError(f"KV_CACHE_DTYPE={self.kv_cache_dtype!r} is not supported "
                              f"(choose one of {', '.join(self.KV_CACHE_DTYPES)})")

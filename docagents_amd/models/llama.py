@@ -26,6 +26,8 @@ weight_dtype="fp8": which products keep an e4m3 copy and which op a decode step 
 planner's answer (ops.keeps_w8_copy, ops.weight_op: ops/gemm_plan.py); this module asks per product
 (``_product``). What it says itself is only which rows are a decode step's: in the plain body a single
 row is; wider rows there are a prefill pass's and stay on gemm() (or the W8A8 route above).
+weight_dtype="mxfp4" follows the same rule one format down (ops.keeps_w4_copy, ops.weight_op with
+weight_dtype="mxfp4"): only the batch-1 GEMVs stream the codes, everything else is the bf16 decoder.
 
 TP layout (rank r of t): local q/k/v heads, F/t FFN features, vocab-parallel lm_head. Generation
 never gathers the [B, V/t] logits: each rank reduces its slice to 8 floats per row (best Gumbel
@@ -260,7 +262,9 @@ class KVCache:
         return cfg.layers * 2 * slots * (cfg.kv_heads // tp_size) * max_seq * row
 
 
-WEIGHT_DTYPES = ("bf16", "fp8")  # fp8: OCP e4m3 weight copy for the batch-1 GEMVs and the 2..128-row decode steps
+# fp8: OCP e4m3 weight copy for the batch-1 GEMVs and the 2..128-row decode steps; mxfp4: OCP MXFP4 weight copy
+# (e2m1 codes + one e8m0 scale per 32 k) for the batch-1 GEMVs only
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
 PREFILL_DTYPES = ("bf16", "fp8")  # fp8: prefill products as e4m3 x e4m3 on that copy, activations quantised per token
 
 
@@ -276,6 +280,9 @@ class LlamaDecoder:
         if weight_dtype == "fp8" and tp is not None and tp.size > 1:
             # quantising per shard is a different model from quantising the whole
             raise ValueError("weight_dtype='fp8' needs TP size 1")
+        if weight_dtype == "mxfp4" and tp is not None and tp.size > 1:
+            # a row-parallel shard's MX blocks are the whole matrix's, but no TP test covers the combination
+            raise ValueError("weight_dtype='mxfp4' needs TP size 1")
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"kv_dtype={kv_dtype!r} is not supported ({' | '.join(KV_DTYPES)})")
         if kv_dtype == "fp8" and tp is not None and tp.size > 1:
@@ -304,6 +311,8 @@ class LlamaDecoder:
         self._fold_norm_gains()
         if weight_dtype == "fp8":
             self._quantise_weights_fp8()
+        elif weight_dtype == "mxfp4":
+            self._quantise_weights_mxfp4()
         self.cos_sin = rope_table(cfg.max_pos, cfg.head_dim, cfg.rope_theta, self.device)
         self.cache: KVCache | None = None
 
@@ -342,16 +351,43 @@ class LlamaDecoder:
                 d[k + "_q8"], d[k + "_s8"] = q, s
             del w, q, s
 
+    def _quantise_weights_mxfp4(self):
+        """weight_dtype="mxfp4": the model IS the quantised model, as with fp8. Every matmul weight is
+        quantised to MXFP4 (ops.quant_weight_mxfp4: e2m1 codes, one power-of-two e8m0 scale per 32 k) and
+        the bf16 tensor is replaced by the dequantised values (exact in bf16): prefill and every step of
+        2+ rows run the bf16 kernels on it, the batch-1 GEMVs stream the codes at 0.53 B per weight. The
+        copy ({name}_q4 uint8 [N, K/2], {name}_e4 uint8 [N, K/32]) is kept where ops.keeps_w4_copy says
+        so; the embedding and the norm gains stay bf16."""
+        o = self.ops
+        prods = [(L, k, e) for L in self.w["layers"]
+                 for k, e in (("wqkv", EPI_NONE), ("wo", EPI_RESID), ("w_gu", EPI_SWIGLU), ("w_down", EPI_RESID))]
+        prods.append((self.w, "lm_head", EPI_NONE))
+        for d, k, epi in prods:
+            w = d[k]
+            if w.shape[1] % 32:
+                raise ValueError(f"weight_dtype='mxfp4' needs K % 32 == 0, {k} has K={w.shape[1]}")
+            q, e = o.quant_weight_mxfp4(w)
+            d[k] = o.dequant_mxfp4(q, e).to(w.dtype).contiguous()
+            if o.keeps_w4_copy(w.shape[0], w.shape[1], epi):
+                d[k + "_q4"], d[k + "_e4"] = q, e
+            del w, q, e
+
     def _product(self, body, d, name, a, **kw):
         """The product a @ d[name]^T as a decode step of layer structure ``body`` runs it (ops.weight_op's
         bodies; ``kw``: the op's keywords): the op ops.weight_op names, on the fp8 copy, where the weight
-        has one (weight_dtype="fp8"); the body's bf16 op on d[name] otherwise."""
+        has one (weight_dtype="fp8"), or ops.gemm_w4 on the MXFP4 copy (weight_dtype="mxfp4"); the body's
+        bf16 op on d[name] otherwise."""
         w, op = d[name], _BF16_OP[body]
         if self.weight_dtype == "fp8" and (name + "_q8") in d:
             op = self.ops.weight_op(body, a.shape[0], w.shape[0], w.shape[1], kw.get("epi", EPI_NONE),
                                     ssq_out=kw.get("ssq_out") is not None)
+        elif self.weight_dtype == "mxfp4" and (name + "_q4") in d:
+            op = self.ops.weight_op(body, a.shape[0], w.shape[0], w.shape[1], kw.get("epi", EPI_NONE),
+                                    ssq_out=kw.get("ssq_out") is not None, weight_dtype="mxfp4")
         if op.endswith("_w8"):
             return getattr(self.ops, op)(a, d[name + "_q8"], d[name + "_s8"], **kw)
+        if op == "gemm_w4":
+            return self.ops.gemm_w4(a, d[name + "_q4"], d[name + "_e4"], **kw)
         return getattr(self.ops, op)(a, w, **kw)
 
     def _row_parallel(self, L, name, a, x, step: bool = False, **route):

@@ -69,6 +69,20 @@ def gemv_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     return M == 1 and _gemv_w8_shape(N, K, epi)
 
 
+def gemv_w4_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
+    """True when gemm_w4() accepts the product: the batch-1 GEMV on MXFP4 weights (csrc/gemv_w4.hip),
+    every shape of the fp8 GEMV's rule (a k-block is 1024 elements there too). No shape is held back:
+    on the five Phi-3-mini products the launch took 0.46-0.69x the bf16 GEMV's time (O projection
+    3.95 vs 5.75 us, the closest), the two runs differing by at most 3 % (profiles/w4/README.md)."""
+    return M == 1 and _gemv_w8_shape(N, K, epi)
+
+
+def keeps_w4_copy(N: int, K: int, epi: int = EPI_NONE) -> bool:
+    """True when a decoder with MXFP4 weights keeps the codes and scales of the [N, K] product: only
+    the one-row GEMV streams them (0.53125 B per weight kept, on top of the bf16 tensor)."""
+    return gemv_w4_fusable(1, N, K, epi)
+
+
 def _dk_shape(N: int, K: int, epi: int) -> bool:
     return K % 256 == 0 and N % 16 == 0 and _decode_epi(N, epi)  # gemm_dk and gemm_dk_w8 alike
 
@@ -291,8 +305,12 @@ def prefill_w8_fusable(M: int, N: int, K: int, epi: int = EPI_NONE) -> bool:
     return not (epi == EPI_RESID and M >= PREFILL_M and underfilled and K <= 3072)
 
 
+_BF16_BODY_OP = {"gemm": "gemm", "dk": "gemm_dk", "resid_norm": "gemm_resid_norm"}
+
+
 @functools.lru_cache(maxsize=4096)
-def weight_op(body: str, M: int, N: int, K: int, epi: int = EPI_NONE, *, ssq_out: bool = False) -> str:
+def weight_op(body: str, M: int, N: int, K: int, epi: int = EPI_NONE, *, ssq_out: bool = False,
+              weight_dtype: str = "fp8") -> str:
     """The name of the op a decoder calls for an M-row product on a weight that has an fp8 copy (the
     bf16 op's name where the product stays on the bf16 tensor). ``body`` is the layer structure asking:
 
@@ -305,7 +323,16 @@ def weight_op(body: str, M: int, N: int, K: int, epi: int = EPI_NONE, *, ssq_out
                   dk kernel writes the parts and gemm_dk_splitk_w8 would refuse), else gemm_dk.
     "resid_norm"  the fused-norm body's O and down projections: gemm_resid_norm_w8 or gemm_resid_norm.
 
-    The W8A8 prefill is no entry here: it swaps the activation operand too (prefill_w8_fusable)."""
+    The W8A8 prefill is no entry here: it swaps the activation operand too (prefill_w8_fusable).
+
+    weight_dtype="mxfp4" (the weight has an MXFP4 copy instead): gemm_w4 for the "gemm" body at one row
+    where gemv_w4_fusable holds; everything else is the body's bf16 op on the dequantised tensor."""
+    if weight_dtype == "mxfp4":
+        if body not in _BF16_BODY_OP:
+            raise ValueError(f"weight_op: unknown body {body!r}")
+        return "gemm_w4" if body == "gemm" and gemv_w4_fusable(M, N, K, epi) else _BF16_BODY_OP[body]
+    if weight_dtype != "fp8":
+        raise ValueError(f"weight_op: unknown weight_dtype {weight_dtype!r}")
     if body == "gemm":
         if gemv_w8_fusable(M, N, K, epi):
             return "gemm_w8"

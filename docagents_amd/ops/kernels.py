@@ -19,8 +19,10 @@ import torch
 
 from . import gemm_plan
 from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: F401 - re-exported
-                        gemv_fusable, gemv_w8_fusable, keeps_w8_copy, prefill_w8_fusable, tile_w8_fusable, weight_op)
-from .reference import quant_weight_fp8, quant_weight_fp8_pow2  # noqa: F401 - host-side torch, done once at load
+                        gemv_fusable, gemv_w4_fusable, gemv_w8_fusable, keeps_w4_copy, keeps_w8_copy,
+                        prefill_w8_fusable, tile_w8_fusable, weight_op)
+from .reference import (dequant_mxfp4, quant_weight_fp8, quant_weight_fp8_pow2,  # noqa: F401 - host-side torch, done
+                        quant_weight_mxfp4)                                       # once at load
 
 _LIB = None
 _LOCK = threading.Lock()
@@ -44,6 +46,8 @@ _SIGS = {
     "da_gemm_fp8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                     c_int, c_int, c_int, c_int, c_void_p],
     "da_gemv_w8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float,
+                   c_void_p],
+    "da_gemv_w4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float,
                    c_void_p],
     "da_quant_fp8_rows": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "da_layernorm_q": [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p],
@@ -461,6 +465,52 @@ def gemm_w8(a: torch.Tensor, wq: torch.Tensor, sw: torch.Tensor, bias=None, epi:
         return out
     _check(lib().da_gemv_w8(_ptr(a), _ptr(wq), _ptr(sw), _ptr(out), _ptr(bias), _ptr(resid), N, K, epi, _ptr(gamma),
                             float(eps), _stream()), "gemm_w8")
+    return out
+
+
+def gemm_w4(a: torch.Tensor, wq: torch.Tensor, se: torch.Tensor, bias=None, epi: int = EPI_NONE, resid=None,
+            out=None, rms=None) -> torch.Tensor:
+    """out[1, N'] = epi(a[1, K] @ dq(wq, se)[N, K]^T) with MXFP4 weights: e2m1 codes wq uint8 [N, K/2] and
+    e8m0 scale bytes se uint8 [N, K/32] (reference.quant_weight_mxfp4's layout; N' = N/2 for EPI_SWIGLU).
+    rms = (gamma or None, eps): RMSNorm(a) fused, as in gemm(). Anything the kernel would refuse raises
+    ValueError before any launch."""
+    _bf16_cuda(a, "a")
+    _req(wq.is_cuda and wq.dtype == torch.uint8, f"wq must be uint8 (e2m1 codes) on GPU, got {wq.dtype}")
+    _req(se.is_cuda and se.dtype == torch.uint8, f"se must be uint8 (e8m0 scales) on GPU, got {se.dtype}")
+    _req(a.dim() == 2 and wq.dim() == 2 and se.dim() == 2, "gemm_w4 expects 2-D operands")
+    M, K = a.shape
+    N = wq.shape[0]
+    _req(wq.shape[1] * 2 == K, f"K mismatch {K} vs {wq.shape[1] * 2} (two codes per byte)")
+    _req(gemv_w4_fusable(M, N, K, epi), f"gemm_w4 does not take M={M} N={N} K={K} epi={epi}")
+    _req(se.shape == (N, K // 32), f"se must be [N, K/32] = {(N, K // 32)}, got {tuple(se.shape)}")
+    _req(a.stride(1) == 1, "a must be a contiguous row")
+    _req(wq.is_contiguous() and se.is_contiguous(), "wq and se must be contiguous")
+    _req(a.data_ptr() % 16 == 0 and wq.data_ptr() % 16 == 0 and se.data_ptr() % 16 == 0,
+         "operands must be 16-B aligned")
+    nout = N // 2 if epi == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, nout), dtype=torch.bfloat16, device=a.device)
+    _bf16_cuda(out, "out")
+    _req(out.shape == (M, nout) and out.stride(1) == 1, "bad out")
+    if bias is not None:
+        _bf16_cuda(bias, "bias"); _req(bias.numel() == N and bias.is_contiguous(), "bias must be [N]")
+        _req(epi in (EPI_BIAS, EPI_RESID), "bias only with BIAS/RESID epilogues")
+    if epi == EPI_RESID:
+        _req(resid is not None, "EPI_RESID needs resid")
+        _bf16_cuda(resid, "resid")
+        _req(resid.shape == (M, N) and resid.stride(1) == 1, "bad resid")
+    else:
+        resid = None
+    gamma, eps = (None, 0.0) if rms is None else rms
+    if rms is not None:
+        _req(eps > 0, "fused RMSNorm needs eps > 0")
+        if gamma is not None:
+            _bf16_cuda(gamma, "gamma")
+            _req(gamma.numel() == K and gamma.is_contiguous() and gamma.data_ptr() % 16 == 0, "gamma must be [K]")
+    if N == 0:
+        return out
+    _check(lib().da_gemv_w4(_ptr(a), _ptr(wq), _ptr(se), _ptr(out), _ptr(bias), _ptr(resid), N, K, epi, _ptr(gamma),
+                            float(eps), _stream()), "gemm_w4")
     return out
 
 

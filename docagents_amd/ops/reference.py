@@ -18,7 +18,8 @@ EPI_ROPE = 6  # gemm8p only: QKV + RoPE + KV-cache write
 # No routing rule of its own: these ARE the planner's objects (pure Python), so a CPU decoder takes
 # the route the GPU one does. The DECODE_DK switch is read where it lives, gemm_plan.DECODE_DK.
 from .gemm_plan import (DK_MAX_M, DK_SPLITK_ABOVE, dk_fusable, dk_parts, dk_w8_fusable,  # noqa: E402,F401
-                        gemv_fusable, gemv_w8_fusable, keeps_w8_copy, prefill_w8_fusable, tile_w8_fusable, weight_op)
+                        gemv_fusable, gemv_w4_fusable, gemv_w8_fusable, keeps_w4_copy, keeps_w8_copy,
+                        prefill_w8_fusable, tile_w8_fusable, weight_op)
 
 
 def gemm_route(M, N, K, epi=EPI_NONE):
@@ -505,6 +506,57 @@ def quant_weight_fp8_pow2(w):
     s = torch.where(amax / (s / 2) <= 448.0, s / 2, s)
     s = torch.where(amax > 0, s, torch.ones_like(s))
     return (wf / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).contiguous(), s.contiguous()
+
+
+# ----------------------------------------------------------------------------------- MXFP4 weights
+# OCP microscaling fp4: e2m1 codes (sign in bit 3, magnitude index into E2M1_GRID in bits 2:0), two
+# per byte (element 2j in bits 3:0 of byte j, element 2j+1 in bits 7:4), and one e8m0 scale byte
+# (e + 127) per 32 consecutive elements of a row.
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MX_BLOCK = 32
+
+
+def quant_weight_mxfp4(w):
+    """MXFP4 weight quantisation (host-side torch; done once at load) -> (codes uint8 [N, K/2],
+    scales uint8 [N, K/32]); K % 32 == 0. Per block of 32 consecutive k of a row: e = the smallest
+    integer with amax / 2^e <= 6 (no clipping: the rule of quant_weight_fp8_pow2, not the OCP floor
+    rule), clamped to [-126, 127], 0 for an all-zero block; the byte is e + 127, so bytes 0 and 255
+    (the e8m0 NaN) never occur. w / 2^e is rounded to the nearest of E2M1_GRID, ties to the even
+    mantissa (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); what rounds to
+    zero is stored as code 0, never -0. An e2m1 value times a power of two is exact in bf16, so
+    dequant_mxfp4 of the result IS a bf16 matrix (magnitudes above 3.5 * 2^126, which no weight has,
+    would round up to 2^128, past the bf16 range)."""
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"quant_weight_mxfp4 needs K % {MX_BLOCK} == 0, got K={K}")
+    wf = w.float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = wf.abs().amax(dim=-1)
+    # amax = m * 2^x, m in [0.5, 1); 6 = 0.75 * 2^3: amax / 2^e <= 6 <=> e >= x - 3 (m <= 0.75), x - 2 (else)
+    m, x = torch.frexp(amax)
+    e = (x - 3 + (m > 0.75).to(x.dtype)).clamp(-126, 127)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    v = torch.ldexp(wf, -e[..., None])
+    a = v.abs()
+    # the index on the grid: one step per midpoint passed; a tie stays below an odd index and goes up to an even one
+    idx = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (idx | (((v < 0) & (idx > 0)).to(torch.uint8) << 3)).reshape(N, K)
+    packed = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return packed, (e + 127).to(torch.uint8).contiguous()
+
+
+def dequant_mxfp4(codes, scales):
+    """bf16 [N, K] of MXFP4 codes [N, K/2] and scale bytes [N, K/32]: exact (see quant_weight_mxfp4)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    c = torch.stack([codes & 0xF, codes >> 4], dim=-1).reshape(N, K).long()
+    grid = torch.tensor(E2M1_GRID, dtype=torch.float32, device=codes.device)
+    val = torch.where((c & 8) != 0, -grid[c & 7], grid[c & 7])
+    e = (scales.to(torch.int32) - 127).repeat_interleave(MX_BLOCK, dim=1)
+    return torch.ldexp(val, e).to(torch.bfloat16)
+
+
+def gemm_w4(a, wq, se, bias=None, epi=EPI_NONE, resid=None, out=None, rms=None):
+    """gemv_w4.hip: gemm() (with its fused RMSNorm on the bf16-normalised row) on the dequantised matrix."""
+    return gemm(a, dequant_mxfp4(wq, se), bias=bias, epi=epi, resid=resid, out=out, rms=rms)
 
 
 # ----------------------------------------------------------------------------------- fp8 vector index
