@@ -201,6 +201,36 @@ def _i32(t, name):
     _req(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous(), f"{name} must be contiguous int32 on GPU")
 
 
+MAX_ROW_D = 16384  # norm.hip: 8 chunks of 8 elements per thread, 256 threads
+
+
+def _row_d(D: int, name: str):
+    _req(D % 8 == 0 and 0 < D <= MAX_ROW_D, f"{name}: D = {D} must be a multiple of 8, at most {MAX_ROW_D}")
+
+
+def _row_vec(t, D: int, dtype, name: str):
+    """A [D] operand the launcher reads as D contiguous elements of dtype."""
+    _req(t.is_cuda and t.dtype == dtype and t.numel() == D and t.is_contiguous(), f"{name} must be contiguous {dtype} [D]")
+
+
+def _row_table(t, D: int, dtype, name: str):
+    _req(t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == D and t.is_contiguous(),
+         f"{name} must be contiguous {dtype} [rows, D]")
+
+
+def _row_out(t, rows: int, D: int, dtype, name: str):
+    """An output the launcher writes as `rows` contiguous rows of D elements of dtype."""
+    _req(t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == D and t.shape[0] >= rows
+         and t.is_contiguous(), f"{name} must be contiguous {dtype} [>= {rows}, {D}]")
+
+
+def _pool_outs(B: int, D: int, out32, out16):
+    if out32 is not None:
+        _row_out(out32, B, D, torch.float32, "out32")
+    if out16 is not None:
+        _row_out(out16, B, D, torch.bfloat16, "out16")
+
+
 # ----------------------------------------------------------------------------------- GEMM
 _WS = {}
 _ROLE = threading.local()
@@ -415,6 +445,7 @@ def quant_fp8(x: torch.Tensor, out=None, scale=None):
     _bf16_cuda(x, "x")
     _req(x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.shape[1] % 8 == 0, "x layout")
     M, K = x.shape
+    _row_d(K, "quant_fp8")
     if out is None:
         out = torch.empty((M, K), dtype=FP8, device=x.device)
     if scale is None:
@@ -734,8 +765,9 @@ def rmsnorm(x, w, eps: float, resid=None, out=None, route_m: int = 0):
     row's squares in another order), so a subset of that pass's rows gets the pass's bits."""
     _bf16_cuda(x, "x"); _bf16_cuda(w, "w")
     M, D = x.shape
-    _req(x.stride(1) == 1 and x.stride(0) % 8 == 0 and D % 8 == 0, "x must be row-major, D % 8 == 0")
-    _req(w.numel() == D, "w must be [D]")
+    _req(x.stride(1) == 1 and x.stride(0) % 8 == 0, "x must be row-major")
+    _row_d(D, "rmsnorm")
+    _row_vec(w, D, torch.bfloat16, "w")
     if resid is not None:
         _bf16_cuda(resid, "resid"); _req(resid.is_contiguous() and resid.shape == (M, D), "resid must be [M, D]")
     if out is None:
@@ -773,11 +805,16 @@ def layernorm(x, g, b, eps: float, resid=None, out=None, fp8_out: bool = False):
     (fused: the row is quantised from registers) -> (y, yq, yscale)."""
     _bf16_cuda(x, "x")
     M, D = x.shape
-    _req(x.is_contiguous() and D % 8 == 0, "x must be contiguous, D % 8 == 0")
+    _req(x.is_contiguous(), "x must be contiguous")
+    _row_d(D, "layernorm")
     if resid is not None:
-        _req(resid.is_contiguous() and resid.shape == x.shape, "bad resid")
+        _bf16_cuda(resid, "resid"); _req(resid.is_contiguous() and resid.shape == x.shape, "bad resid")
+    _row_vec(g, D, torch.bfloat16, "g")
+    if b is not None:
+        _row_vec(b, D, torch.bfloat16, "b")
     if out is None:
         out = torch.empty_like(x)
+    _row_out(out, M, D, torch.bfloat16, "out")
     if fp8_out:
         yq = torch.empty((M, D), dtype=FP8, device=x.device)
         ys = torch.empty(M, dtype=torch.float32, device=x.device)
@@ -794,10 +831,16 @@ def bert_embed_ln(ids, positions, types, word, pos, type_, g, b, eps: float, out
     if types is not None:
         _i32(types, "types")
     T = ids.numel()
+    _req(word.dim() == 2, "word must be [rows, D]")
     D = word.shape[1]
-    _req(positions.numel() == T, "positions length")
+    _req(positions.numel() == T and (types is None or types.numel() == T), "positions / types length")
+    _row_d(D, "bert_embed_ln")
+    for t, n in ((word, "word"), (pos, "pos"), (type_, "type")):
+        _row_table(t, D, torch.bfloat16, n)
+    _row_vec(g, D, torch.bfloat16, "g"); _row_vec(b, D, torch.bfloat16, "b")
     if out is None:
         out = torch.empty((T, D), dtype=torch.bfloat16, device=ids.device)
+    _row_out(out, T, D, torch.bfloat16, "out")
     if fp8_out:
         yq = torch.empty((T, D), dtype=FP8, device=ids.device)
         ys = torch.empty(T, dtype=torch.float32, device=ids.device)
@@ -812,9 +855,13 @@ def bert_embed_ln(ids, positions, types, word, pos, type_, g, b, eps: float, out
 
 def embed(ids, table, out=None):
     _i32(ids, "ids"); _bf16_cuda(table, "table")
+    _req(table.dim() == 2, "table must be [rows, D]")
     T, D = ids.numel(), table.shape[1]
+    _row_d(D, "embed")
+    _row_table(table, D, torch.bfloat16, "table")
     if out is None:
         out = torch.empty((T, D), dtype=torch.bfloat16, device=ids.device)
+    _row_out(out, T, D, torch.bfloat16, "out")
     _check(lib().da_embed(_ptr(ids), _ptr(table), _ptr(out), T, D, _stream()), "embed")
     return out
 
@@ -822,10 +869,12 @@ def embed(ids, table, out=None):
 def pool_l2norm(h, cu_seqlens, mode: int = 0, out32=None, out16=None):
     _bf16_cuda(h, "h"); _i32(cu_seqlens, "cu_seqlens")
     B = cu_seqlens.numel() - 1
+    _req(h.dim() == 2 and h.is_contiguous() and B >= 0, "h must be contiguous [T, D]")
     D = h.shape[1]
-    _req(h.is_contiguous(), "h contiguous")
+    _row_d(D, "pool_l2norm")
     if out32 is None and out16 is None:
         out32 = torch.empty((B, D), dtype=torch.float32, device=h.device)
+    _pool_outs(B, D, out32, out16)
     _check(lib().da_pool_l2norm(_ptr(h), _ptr(cu_seqlens), B, D, mode, _ptr(out32), _ptr(out16), _stream()),
            "pool_l2norm")
     return out32 if out32 is not None else out16
@@ -1541,12 +1590,16 @@ def flash_attn_f16(q, k, v, cu_seqlens, max_seqlen: int, H: int, Hkv: int, D: in
 def layernorm_f16(x, g, b, eps: float, resid=None, out=None):
     _f16_cuda(x, "x")
     M, D = x.shape
-    _req(x.is_contiguous() and D % 8 == 0, "x must be contiguous, D % 8 == 0")
+    _req(x.is_contiguous(), "x must be contiguous")
+    _row_d(D, "layernorm_f16")
     if resid is not None:
         _f16_cuda(resid, "resid"); _req(resid.is_contiguous() and resid.shape == x.shape, "bad resid")
-    _f16_cuda(g, "g"); _f16_cuda(b, "b")
+    _row_vec(g, D, torch.float16, "g")
+    if b is not None:
+        _row_vec(b, D, torch.float16, "b")
     if out is None:
         out = torch.empty_like(x)
+    _row_out(out, M, D, torch.float16, "out")
     _check(lib().da_layernorm_f16(_ptr(x), _ptr(resid), _ptr(g), _ptr(b), _ptr(out), M, D, float(eps), _stream()),
            "layernorm_f16")
     return out
@@ -1554,12 +1607,18 @@ def layernorm_f16(x, g, b, eps: float, resid=None, out=None):
 
 def bert_embed_ln_f16(ids, positions, types, word, pos, type_, g, b, eps: float, out=None):
     _i32(ids, "ids"); _i32(positions, "positions")
-    for t, n in ((word, "word"), (pos, "pos"), (type_, "type"), (g, "g"), (b, "b")):
-        _f16_cuda(t, n)
+    if types is not None:
+        _i32(types, "types")
+    _req(word.dim() == 2, "word must be [rows, D]")
     T, D = ids.numel(), word.shape[1]
-    _req(positions.numel() == T and D % 8 == 0, "positions length / D")
+    _req(positions.numel() == T and (types is None or types.numel() == T), "positions / types length")
+    _row_d(D, "bert_embed_ln_f16")
+    for t, n in ((word, "word"), (pos, "pos"), (type_, "type")):
+        _row_table(t, D, torch.float16, n)
+    _row_vec(g, D, torch.float16, "g"); _row_vec(b, D, torch.float16, "b")
     if out is None:
         out = torch.empty((T, D), dtype=torch.float16, device=ids.device)
+    _row_out(out, T, D, torch.float16, "out")
     _check(lib().da_bert_embed_ln_f16(_ptr(ids), _ptr(positions), _ptr(types), _ptr(word), _ptr(pos), _ptr(type_),
                                       _ptr(g), _ptr(b), _ptr(out), T, D, float(eps), _stream()), "bert_embed_ln_f16")
     return out
@@ -1568,12 +1627,12 @@ def bert_embed_ln_f16(ids, positions, types, word, pos, type_, g, b, eps: float,
 def pool_l2norm_f16(h, cu_seqlens, mode: int = 0, out32=None, out16=None):
     """fp16 hidden states -> unit-norm pooled rows, fp32 and / or bf16 (the index storage type)."""
     _f16_cuda(h, "h"); _i32(cu_seqlens, "cu_seqlens")
+    _req(h.dim() == 2 and h.is_contiguous(), "h must be contiguous [T, D]")
     B, D = cu_seqlens.numel() - 1, h.shape[1]
-    _req(h.is_contiguous() and D % 8 == 0, "h contiguous")
-    if out16 is not None:
-        _bf16_cuda(out16, "out16")
+    _row_d(D, "pool_l2norm_f16")
     if out32 is None and out16 is None:
         out32 = torch.empty((B, D), dtype=torch.float32, device=h.device)
+    _pool_outs(B, D, out32, out16)
     _check(lib().da_pool_l2norm_f16(_ptr(h), _ptr(cu_seqlens), B, D, mode, _ptr(out32), _ptr(out16), _stream()),
            "pool_l2norm_f16")
     return out32 if out32 is not None else out16

@@ -225,7 +225,7 @@ def test_layernorm_and_embed(D):
     ps = torch.randint(0, 64, (23,), device=DEV, dtype=torch.int32)
     _close(K.bert_embed_ln(ids, ps, None, word, pos, typ, g, b, 1e-12),
            R.bert_embed_ln(ids, ps, None, word, pos, typ, g, b, 1e-12), atol=0.03)
-    _close(K.embed(ids, word), R.embed(ids, word), atol=0)
+    assert torch.equal(K.embed(ids, word), R.embed(ids, word))  # a gather is a copy
 
 
 @pytest.mark.parametrize("mode", [0, 1])
